@@ -11,8 +11,11 @@ GPU.  Filters are independent, so N GPUs run N x batch filters with no data-path
         --master-port P bench.py --gpus N --steps K --warmup W
 
 Prints ONE JSON line on rank 0 (contract in the task statement), with `roofline` (dominant kernel,
-HIP-event timed on the launch stream) and `cpu_baseline` (the CPU oracle = a port of the
-reference's dense algorithm, timed on this host's cores on a bounded sample).
+HIP-event timed on the launch stream).  A plain run sets up, warms up, times the K steps and prints;
+`--full` adds the checker and secondary legs: parity vs the CPU oracle and `cpu_baseline` (a port of
+the reference's dense algorithm, timed on this host's cores on a bounded sample), the `no_prewarm`
+figure, the cadence / single-filter / sequencer routes and the other BASELINE configs.
+`--dump-outputs DIR` writes what the timed path computed in its last step (rank 0's filters) as .npy.
 """
 import argparse
 import json
@@ -27,6 +30,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec
+DUMP_BYTES = 60 * 10 ** 6  # --dump-outputs: the arrays' budget (under 64 MB with the .npy headers and the filter lists)
 
 
 def shard(total, world, rank):
@@ -250,6 +254,30 @@ def secondary_config(v, scene, torch, dev, dev_index, B, N, K, W, parity_steps, 
     return out
 
 
+def dump_outputs(dirname, g, res_last):
+    """--dump-outputs: what a caller of the timed path holds after its last step -> DIR/<name>.npy.  `state` x [.][nx] and
+    `result` (that step's update codes, float32) [.][M] get a quarter of the DUMP_BYTES budget, `covariance` P [.][n][n] the
+    rest; where a batch's rows pass their share, a fixed seeded sample of filters is written and `state_filters` (also the rows
+    of `result`) / `covariance_filters` list them."""
+    os.makedirs(dirname, exist_ok=True)
+    B = g.B
+
+    def rows(row_bytes, budget):
+        k = min(B, max(1, budget // row_bytes))
+        return np.arange(B) if k == B else np.sort(np.random.default_rng(0xD1FF).choice(B, k, replace=False))
+
+    res = res_last.cpu().numpy().astype(np.float32)
+    r1 = rows(g.nx * 8 + res.shape[1] * 4, DUMP_BYTES // 4)
+    r2 = rows(g.n * g.n * 8, DUMP_BYTES - DUMP_BYTES // 4)
+    out = {"state": g.get_state()[r1], "result": res[r1], "covariance": g.get_covariance()[r2]}
+    if len(r1) < B:
+        out["state_filters"] = r1.astype(np.float64)
+    if len(r2) < B:
+        out["covariance_filters"] = r2.astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+
+
 def flops_block(N, steps_per_s):
     """Structured algorithmic flops of one step: Phi P Phi^T + G Q G^T + N rank-2 Lambda-masked sweeps, priced against
     the part's fp64 peak (the secondary ceiling of SURVEY 8d: the fused step's intensity is above the fp64 ridge)."""
@@ -277,14 +305,21 @@ def main():
     ap.add_argument("--kernel", type=int, default=0, help="0 auto, 1 streaming, 2 resident")
     ap.add_argument("--tune", action="append", default=[], metavar="KEY=VALUE",
                     help="viekf_batch_set_tuning(KEY, VALUE) on the benchmarked batch (integers, include/viekf.h VIEKF_TUNE_*): A/B runs")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the cadence run (profiling: keeps the kernel statistics to the timed steps)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checker and secondary legs (oracle parity, CPU baseline, no_prewarm, cadence, single filter, "
+                         "sequencer routes, other BASELINE configs); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write state / covariance / result of the last timed step (rank 0's filters) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the oracle parity and CPU baseline legs")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the cadence, single-filter, sequencer and config legs")
     ap.add_argument("--prewarm-ms", type=float, default=60.0,
                     help="milliseconds of the same step run untimed BEFORE the W warm-up steps (a GPU that was just handed over idles at "
-                         "low clocks); 0 = none. The figure for the bare command-line contract is always reported too (no_prewarm)")
+                         "low clocks); 0 = none. With --full the figure for the bare command-line contract is reported too (no_prewarm)")
     ap.add_argument("--cpu-filters", type=int, default=0)
     ap.add_argument("--cpu-steps", type=int, default=0)
     args = ap.parse_args()
+    checks = args.full and not args.no_cpu_baseline           # parity vs the oracle (+ the CPU baselines)
+    secondary = args.full and not args.no_secondary
 
     import torch
     import torch.distributed as dist
@@ -351,7 +386,7 @@ def main():
     #      and -- rank 0 of the N=1 run only -- the CPU baselines on a bounded sample of the same workload
     cpu = None
     parity = 0.0
-    if not args.no_cpu_baseline:
+    if checks:
         ncpu = os.cpu_count() or 1
         n = 16 + 3 * N
         flop = (8 + 4 * N) * float(n) ** 3      # dense cost per filter-step; ~6 GFLOP/s per thread for the plain-C loops
@@ -400,9 +435,9 @@ def main():
 
     # ---- phase B: warmup + timed region
     # A GPU that has just been handed over idles at low clocks: the first ~10 ms of launches run 8 % slower (measured: 20 timed
-    # steps after 5 warm-up steps 0.378 ms per step, after 150 more 0.359).  The region is therefore timed TWICE with exactly the
-    # command line's W warm-up + K timed steps: first as the bare contract has it (reported as `no_prewarm`, comparable with the
-    # r01 / r02 driver figures), then again after --prewarm-ms of the same step (reported as prewarm_steps); `value` is the second.
+    # steps after 5 warm-up steps 0.378 ms per step, after 150 more 0.359).  `value` times exactly the command line's W warm-up +
+    # K timed steps after --prewarm-ms of the same step (reported as prewarm_steps); --full times the region once more before
+    # that, as the bare contract has it (reported as `no_prewarm`, comparable with the r01 / r02 driver figures).
     def timed_region(with_events):
         init_filters()
         for s in range(W):
@@ -432,8 +467,9 @@ def main():
         torch.cuda.synchronize()
         return time.perf_counter() - t0, ev, marks
 
-    secs_cold, _, _ = timed_region(False)
-    secs_cold = reduce_times(secs_cold, world)
+    if args.full:
+        secs_cold, _, _ = timed_region(False)
+        secs_cold = reduce_times(secs_cold, world)
     prewarm = 0
     if args.prewarm_ms > 0:
         init_filters()
@@ -445,6 +481,8 @@ def main():
                 torch.cuda.synchronize()
         torch.cuda.synchronize()
     secs, ev, marks = timed_region(True)
+    if args.dump_outputs and rank == 0:    # before any --full leg steps these filters again
+        dump_outputs(args.dump_outputs, g, d_res_all[K - 1])
     alg_bytes = scene.algorithmic_bytes_per_step(N) * B  # one launch processes B filter-steps
     rec = reduce_record(B * K, secs, alg_bytes * K, parity, world)
     secs = rec["seconds"]
@@ -462,10 +500,10 @@ def main():
     # ---- secondary numbers, outside the contract's timed region: the realistic cadence 25 IMU propagates :
     #      3 camera frames (250 Hz : 30 Hz, params/sim_params.yaml:149,160) -- 22 propagate-only launches + 3 full steps
     cadence = None
-    if world == 1 and not args.no_secondary:
+    if world == 1 and secondary:
         cyc = 4
         cad_par = None
-        if not args.no_cpu_baseline:
+        if checks:
             # what this leg times, checked first: one 25-sample cycle of both routes from freshly initialised
             # filters against the oracle (K vo_propagate + the frame's updates) on a strided sample; outside every timed window
             cad_par = cadence_parity(g, sc, N, params, uniq, init_filters, step, d_u, d_dt, d_z, d_slot, d_R, d_res, torch)
@@ -510,7 +548,7 @@ def main():
 
     # ... and the reference's own CPU-runnable case (BASELINE configs[0]): ONE filter, N_feat = 12, step latency
     single = None
-    if world == 1 and not args.no_secondary:
+    if world == 1 and secondary:
         try:
             sc1 = scene.make_scene(1, 12, 8, seed=5)
             g1 = v.BatchVIEKF(1, 12, sc1["params"], device=dev_index)
@@ -534,11 +572,11 @@ def main():
     # ... and the DROP-IN route: the same filters driven through viekf_seq_propagate / _add_frame /
     # _handle_measurements at 250 Hz : 30 Hz with the camera's 30 ms delay -- every frame rewinds and replays (tools/seq_bench.py)
     seq_cad = None
-    if world == 1 and not args.no_secondary:
+    if world == 1 and secondary:
         try:
             sys.path.insert(0, os.path.join(ROOT, "tools"))
             import seq_bench
-            pf = 0 if args.no_cpu_baseline else 5      # frames flown against oracle/seq_oracle.SeqOracle before the timed run
+            pf = 5 if checks else 0      # frames flown against oracle/seq_oracle.SeqOracle before the timed run
             seq_cad = {"shared_clock": seq_bench.run(B, N, False, 40, parity_frames=pf),
                        "independent_clocks": seq_bench.run(B, N, True, 24, parity_frames=pf)}
             if cadence is not None:
@@ -551,12 +589,12 @@ def main():
     # ... and the other single-GPU BASELINE configs (VERDICT r03 missing #3): configs[1] B=256, N=25 and configs[4] B=1024, N=150
     # (5 warm-up + 20 timed steps), each with its own algorithmic bytes, kernel description and in-run parity figure
     configs = None
-    if world == 1 and not args.no_secondary and (B, N) == (1024, 50):
+    if world == 1 and secondary and (B, N) == (1024, 50):
         configs = {}
         for name, cb, cn, ck, cw, psteps, pfilters in (("b256_n25", 256, 25, 200, 20, 3, 8), ("b1024_n150", 1024, 150, 20, 5, 1, 2)):
             try:
                 configs[name] = secondary_config(v, scene, torch, dev, dev_index, cb, cn, ck, cw, psteps,
-                                                 0 if args.no_cpu_baseline else pfilters)
+                                                 pfilters if checks else 0)
             except SystemExit:
                 raise
             except Exception as e:
@@ -589,8 +627,6 @@ def main():
             "steps": K,
             "warmup": W,
             "prewarm_steps": prewarm,
-            "no_prewarm": {"ms_per_step": secs_cold / K * 1e3, "value": B * world * K / secs_cold,
-                           "what": "the same W warm-up + K timed steps run first, straight after set-up (no --prewarm-ms)"},
             "ms_per_step": secs / K * 1e3,
             "higher_is_better": True,
             "scaling": "weak",
@@ -616,6 +652,9 @@ def main():
             "reduction": rec,
         }
         out["flops"] = flops_block(N, B / launch_s)
+        if args.full:
+            out["no_prewarm"] = {"ms_per_step": secs_cold / K * 1e3, "value": B * world * K / secs_cold,
+                                 "what": "the same W warm-up + K timed steps run first, straight after set-up (no --prewarm-ms)"}
         if cadence is not None:
             out["cadence_250_30"] = cadence
         if single is not None:
@@ -626,7 +665,7 @@ def main():
             out["configs"] = configs
         if cpu is not None:
             out["cpu_baseline"] = cpu
-        if not args.no_cpu_baseline:
+        if checks:
             out["parity_max_rel_err"] = rec["max_rel_err"]
         print(json.dumps(out))
     if world > 1:

@@ -25,7 +25,7 @@ def test_two_ranks_on_one_card_step_their_shards_and_reduce_one_record():
     env = dict(os.environ, VIEKF_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", str(steps), "--warmup", str(warm),
-           "--batch", str(B), "--no-secondary"]     # (the parity leg stays on: every rank checks 8 of its filters)
+           "--batch", str(B), "--full", "--no-secondary"]     # (the parity leg stays on: every rank checks 8 of its filters)
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -7,7 +7,7 @@ cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 OUT=gpurun_out/prof4
 rm -rf $OUT; mkdir -p $OUT
-python3 bench.py > $OUT/bench.json 2> $OUT/bench.err
+python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 run() {   # tag, bench args, steps, warmup
   local tag=$1 args=$2 k=$3 w=$4
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${tag}_stats -- python3 bench.py $args --steps $k --warmup $w --no-cpu-baseline --no-secondary > $OUT/${tag}_stats.log 2>&1
