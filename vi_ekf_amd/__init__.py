@@ -7,3 +7,4 @@ from . import capi, scene  # noqa: F401
 from .batch import BatchVIEKF  # noqa: F401
 from .capi import Params, ViekfError, device_count, load_yaml  # noqa: F401
 from .seq import SeqVIEKF  # noqa: E402,F401
+from .klt import KLTTracker, track_frame  # noqa: E402,F401

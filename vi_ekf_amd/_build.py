@@ -10,6 +10,7 @@ CSRC = os.path.join(HERE, "csrc")
 def sources():
     out = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".cpp", ".hpp", "Makefile"))]
     out.append(os.path.join(os.path.dirname(HERE), "include", "viekf.h"))
+    out.append(os.path.join(os.path.dirname(HERE), "include", "viekf_klt.h"))
     return out
 
 

@@ -52,6 +52,8 @@ std::mutex g_attr_mutex;
 
 }  // namespace
 
+int viekf::set_last_error(int code, const std::string& msg) { return fail(code, msg); }
+
 struct viekf_batch {
   int B = 0, N = 0, nx = 0, nxs = 0, n = 0, ld = 0, device = 0;
   viekf_params params;

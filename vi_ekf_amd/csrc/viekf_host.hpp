@@ -10,5 +10,7 @@ typedef std::map<std::string, std::string> YamlMap;
 bool yaml_parse_file(const std::string& path, YamlMap& out, std::string& err);
 bool yaml_get_doubles(const YamlMap& m, const std::string& key, double* out, int count, std::string& err);
 bool yaml_get_string(const YamlMap& m, const std::string& key, std::string& out, std::string& err);
+// records `msg` as this thread's viekf_last_error() and returns `code` (for the C-ABI files other than viekf_capi.hip)
+int set_last_error(int code, const std::string& msg);
 
 }  // namespace viekf

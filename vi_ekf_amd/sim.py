@@ -184,6 +184,41 @@ class Simulator:
         z = pix[lm] + self.rng.normal(0, self.pix_sigma, (len(lm), 2))
         return z, [self.feat_id[i] for i in lm], depth[lm]
 
+    def render(self, width=640, height=480, depth=False):
+        """-> GRAY8 image [height][width] (and, with depth=True, float32 range in mm) of the textured ground plane z = 0 seen
+        through the pinhole model of project(): a Gaussian blob on every landmark plus smooth shading, by ray-plane
+        intersection.  Deterministic in the truth state; does not draw from self.rng."""
+        v, u = np.mgrid[0:height, 0:width].astype(np.float64)
+        dc = np.stack([(u - self.c[0]) / self.f[0], (v - self.c[1]) / self.f[1], np.ones_like(u)], -1).reshape(-1, 3)
+        Rbc = np.stack([q_rota(self.q_b_c, e) for e in np.eye(3)], 1)        # camera -> body
+        Rib = np.stack([q_rota(self.q, e) for e in np.eye(3)], 1)            # body -> inertial
+        d = dc @ (Rib @ Rbc).T
+        C = self.pos + q_rota(self.q, self.p_b_c)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            t = -C[2] / d[:, 2]
+        hit = np.isfinite(t) & (t > 0)
+        t = np.where(hit, t, 0.0)
+        X, Y = C[0] + t * d[:, 0], C[1] + t * d[:, 1]
+        g = np.arange(-3.0, 3.0001, 0.22)
+        ng = len(g)
+        fi, fj = np.floor((X - g[0]) / 0.22).astype(int), np.floor((Y - g[0]) / 0.22).astype(int)
+        blobs = np.zeros_like(X)
+        for di in (0, 1):                        # the four grid nodes around the point (blobs further away are < 1e-2)
+            for dj in (0, 1):
+                i, j = fi + di, fj + dj
+                ok = (i >= 0) & (i < ng) & (j >= 0) & (j < ng)
+                k = np.where(ok, i * ng + j, 0)
+                amp = 0.55 + 0.45 * np.sin(12.9898 * k + 4.1414)
+                r2 = (X - self.landmarks[k, 0]) ** 2 + (Y - self.landmarks[k, 1]) ** 2
+                blobs += np.where(ok, amp * np.exp(-r2 * (1.0 / (2 * 0.045 ** 2))), 0.0)
+        shade = 0.5 + 0.25 * np.sin(1.3 * X + 0.4) * np.cos(0.9 * Y - 0.2)
+        img = np.where(hit, 50.0 + 60.0 * shade + 140.0 * np.minimum(blobs, 1.0), 30.0)
+        img = np.clip(np.rint(img), 0, 255).astype(np.uint8).reshape(height, width)
+        if not depth:
+            return img
+        rng_mm = np.where(hit, t * np.linalg.norm(d, axis=1) * 1e3, np.inf).astype(np.float32).reshape(height, width)
+        return img, rng_mm
+
     # -- reference Simulator::run ----------------------------------------------------------------------------------------
     def run(self):
         """one IMU period: truth, then the IMU callback, then (at the camera rate) the feature callback"""
