@@ -151,7 +151,9 @@ int viekf_batch_describe(const viekf_batch *b, char *out, int32_t cap);
 /* state access.  Replaces get_state()/get_covariance()/get_len_features(), include/vi_ekf.h:271-286,
  * and set_x0 / set_imu_bias, src/vi_ekf/vi_ekf.cpp:157-184.  Any pointer may be NULL (skipped).  A covariance handed to
  * set_state is symmetrised, (P + P^T) / 2: the library keeps P exactly symmetric (the reference's Joseph-form update,
- * vi_ekf_meas.cpp:256-257, keeps it symmetric to rounding; the rank-2 form used here is equal to it for symmetric P only). */
+ * vi_ekf_meas.cpp:256-257, keeps it symmetric to rounding; the rank-2 form used here is equal to it for symmetric P only).
+ * A NaN in the active block of that P (rows and columns below dxZ + 3 len_features) raises VIEKF_FLAG_NAN, as the
+ * reference's NaNsInTheHouse (vi_ekf_error.cpp:6-18) would report it; the kernels themselves only test x. */
 int viekf_batch_get_state(viekf_batch *b, double *x, double *P, int32_t *len_features, viekf_mem where);
 int viekf_batch_set_state(viekf_batch *b, const double *x, const double *P, const int32_t *len_features,
                           viekf_mem where);
@@ -169,7 +171,10 @@ int viekf_batch_init_feature(viekf_batch *b, const double *pix /*[batch][2]*/, c
 /* M sequential ACTIVE FEAT updates per filter: VIEKF::update + h_feat,
  * src/vi_ekf/vi_ekf_meas.cpp:196-278,354-367, applied in array order m = 0..M-1
  * (the caller supplies the reference's reverse in-frame order, vi_ekf_meas.cpp:150-176).
- * R: 2x2 column-major; r_mode 0 = one R for all, 1 = R[batch][4], 2 = R[batch][M][4]. */
+ * R: 2x2 column-major; r_mode 0 = one R for all, 1 = R[batch][4], 2 = R[batch][M][4].
+ * Kept deviation, a NaN already in P: the gain is formed from the measured feature's two columns of P only, so the NaN guard
+ * (vi_ekf_meas.cpp:247) skips only the updates whose own columns hold the NaN and the others are applied.  The reference's
+ * dense P H^T (:241-247) makes every later gain NaN (0 x NaN) and so skips every later update of that filter. */
 int viekf_batch_update_feat(viekf_batch *b, const double *z, const int32_t *slot, int32_t M, const double *R,
                             int32_t r_mode, int32_t *result, viekf_mem where);
 
@@ -258,7 +263,9 @@ int viekf_batch_propagate_to(viekf_batch *b, const double *u, const double *dt, 
  * feature changes ...) works on each filter's own slot.  propagate_filters_to: the filters with dst_slot[b] >= 0 step from their
  * live slot INTO dst_slot[b], which becomes their live slot (src/vi_ekf/vi_ekf.cpp:298-306 per filter: the fused kernel loads
  * filter b from slot i_b and stores it into slot i_b + 1, no pass over P besides the step's own); the others are not touched.
- * dst_slot is HOST memory, u / dt as `where` says.  viekf_batch_history_resize(b, 0) brings every live state home again. */
+ * dst_slot is HOST memory, u / dt as `where` says.  viekf_batch_history_resize(b, 0) brings every live state home again.
+ * dst_slot is the call's own participation mask: while one set with viekf_batch_set_active is in force the call returns
+ * VIEKF_ERR_INVALID and changes nothing (like propagate_to); a filter that is to stay put gets dst_slot[b] < 0. */
 int viekf_batch_select_filters(viekf_batch *b, const int32_t *slot);
 int viekf_batch_propagate_filters_to(viekf_batch *b, const double *u, const double *dt, const int32_t *dst_slot, viekf_mem where);
 /* K propagates in a row, step k into ring slot dst_slots[k] (all different, none of them the live slot); the last one becomes the
@@ -312,8 +319,7 @@ int viekf_seq_create(viekf_batch *core, int32_t state_hist, int32_t meas_hist, v
  * stamps, different camera delays) and still share the batch.  Every filter keeps its own time ring, input queue and measurement
  * queue and makes its own handle_measurements decisions (deferral, rewind target, replay length: src/vi_ekf/vi_ekf_meas.cpp:6-127
  * per filter); the device steps of a call are batched over the filters that take the same kind of step (viekf_batch_set_active,
- * viekf_batch_select_filters / _propagate_filters_to: every filter's ring is zero-copy, a rewind is an index).  Each filter's results are those of a batch of one fed the same inputs.  The
- * state history is a snapshot ring here (one copy of (x, P) per propagate, not the zero-copy ring of the shared clock).
+ * viekf_batch_select_filters / _propagate_filters_to: every filter's ring is zero-copy, a rewind is an index).  Each filter's results are those of a batch of one fed the same inputs.
  *   viekf_seq_propagate_t / _add_measurement_t take t [batch] and an optional mask [batch] (0 = this filter has no sample in
  *   this call); viekf_seq_propagate / _add_measurement with one t still work (same stamp for everybody); everything else
  *   (handle_measurements, keep_only_features, init_feature, global pose) is shared.  The log writer is lock-step only. */

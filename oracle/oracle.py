@@ -84,6 +84,8 @@ def lib():
         L.vo_h.argtypes = [_fp, C.c_int, _dp, _dp, _dp, C.c_int]
         L.vo_update.argtypes = [_fp, C.c_int, _dp, C.c_int, _dp, C.c_int, C.c_int, C.c_int]
         L.vo_update.restype = C.c_int
+        L.vo_update_feat_structured.argtypes = [_fp, _dp, _dp, C.c_int]
+        L.vo_update_feat_structured.restype = C.c_int
         L.vo_global_to_local_feature_id.argtypes = [_fp, C.c_int]
         L.vo_global_to_local_feature_id.restype = C.c_int
         L.vo_keyframe_reset.argtypes = [_fp]
@@ -281,6 +283,15 @@ class OracleFilter:
         Rf = np.ascontiguousarray(R.ravel(order="F"))
         return int(self._L.vo_update(self._p, int(mtype), _d(z), int(z.size), _d(Rf), int(R.shape[0]),
                                      int(active), int(id)))
+
+    def update_feat_structured(self, z, R, id):
+        """one ACTIVE FEAT update in the block-sparse / rank-2 form of the HIP kernels (W from the measured feature's two
+        columns of P only); id: the feature's global id, which must be tracked -> VO_MEAS_SUCCESS or VO_MEAS_GATED"""
+        z = _vec(z, 2)
+        Rf = np.ascontiguousarray(np.asarray(R, dtype=np.float64).reshape(2, 2).ravel(order="F"))
+        if self.global_to_local_feature_id(id) < 0:
+            raise ValueError("feature id %d is not tracked" % id)
+        return int(self._L.vo_update_feat_structured(self._p, _d(z), _d(Rf), int(id)))
 
     def keyframe_reset(self): self._L.vo_keyframe_reset(self._p)
 

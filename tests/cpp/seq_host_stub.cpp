@@ -96,7 +96,7 @@ int viekf_batch_select_filters(viekf_batch* b, const int32_t* slot) {
   return VIEKF_OK;
 }
 int viekf_batch_propagate_filters_to(viekf_batch* b, const double* u, const double* dt, const int32_t* dst, viekf_mem) {
-  if (!b->per_filter) return VIEKF_ERR_INVALID;
+  if (!b->per_filter || b->active_on) return VIEKF_ERR_INVALID;
   for (int i = 0; i < b->B; i++) if (dst[i] >= (int)b->rx.size() || (dst[i] >= 0 && dst[i] == b->lf[(size_t)i])) return VIEKF_ERR_INVALID;
   b->calls++;
   for (int i = 0; i < b->B; i++) {

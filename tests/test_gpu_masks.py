@@ -229,3 +229,51 @@ def test_per_filter_live_slots_zero_copy_ring(N, kernel, B):
     assert np.array_equal(ga.get_state(), x_new) and np.array_equal(ga.get_covariance(), Pb)
     ga.propagate(u, dt); gb.set_state(x=x_new); gb.propagate(u, dt)
     assert np.array_equal(ga.get_state(), gb.get_state()) and np.array_equal(ga.get_covariance(), gb.get_covariance())
+
+
+def test_propagate_filters_to_refuses_a_participation_mask():
+    """viekf_batch_propagate_filters_to launches under a mask of its own (dst_slot[b] >= 0): a mask the caller set with
+    viekf_batch_set_active would be ignored and a filter it masked out stepped anyway.  Refused like propagate_to: ERR_INVALID,
+    and x, P, status and the live slot map are what they were; after set_active(NULL) the same call goes through."""
+    B, N, H = 7, 6, 4
+    sc = scene.make_scene(B, N, 2, seed=27)
+    L = capi.lib()
+    g = v.BatchVIEKF(B, N, sc["params"])
+    for i in range(N):
+        g.init_feature(sc["pix"][:, i, :].copy(), np.full(B, np.nan))
+    g.history_resize(H)
+    for s in (2, 3):                                 # slots 2 and 3: the state before the step
+        capi.check(L.viekf_batch_snapshot_filters(g._h, _p(np.full(B, s, dtype=np.int32)), capi.HOST))
+    g.step(sc["u"][0], sc["dt"], sc["z"][0], sc["slot"], sc["R"])
+    live = (np.arange(B) % 2).astype(np.int32)      # slots 0 and 1: the state after it, the live ones
+    capi.check(L.viekf_batch_snapshot_filters(g._h, _p(live), capi.HOST))
+    capi.check(L.viekf_batch_select_filters(g._h, _p(live)))
+    dst = (live + 2).astype(np.int32)
+    dst[3] = -1
+
+    def read():
+        """x, P, status of the live slots, and x, P of the destination slots (selected and selected back)"""
+        out = [g.get_state(), g.get_covariance(), g.get_status()]
+        capi.check(L.viekf_batch_select_filters(g._h, _p(dst)))
+        out += [g.get_state(), g.get_covariance()]
+        capi.check(L.viekf_batch_select_filters(g._h, _p(live)))
+        return out
+
+    before = read()
+    assert not np.array_equal(before[0], before[3])
+    mask = np.array([1, 0, 1, 1, 0, 1, 1], dtype=np.uint8)      # filters 1 and 4 masked out, with dst_slot >= 0
+    capi.check(L.viekf_batch_set_active(g._h, _p(mask), capi.HOST))
+    u, dt = np.ascontiguousarray(sc["u"][1]), np.ascontiguousarray(sc["dt"])
+    assert L.viekf_batch_propagate_filters_to(g._h, _p(u), _p(dt), _p(dst), capi.HOST) == capi.ERR_INVALID
+    capi.check(L.viekf_batch_set_active(g._h, None, capi.HOST))
+    after = read()
+    for a, b in zip(before, after):
+        assert np.array_equal(a, b)
+    capi.check(L.viekf_batch_propagate_filters_to(g._h, _p(u), _p(dt), _p(dst), capi.HOST))
+    x, P = g.get_state(), g.get_covariance()
+    moved = dst >= 0
+    assert np.array_equal(x[~moved], before[0][~moved]) and np.array_equal(P[~moved], before[1][~moved])
+    assert all(not np.array_equal(x[b], before[0][b]) for b in np.flatnonzero(moved))
+    # the moved filters now live in their destination slots: selecting the old live slots shows the states left there
+    capi.check(L.viekf_batch_select_filters(g._h, _p(live)))
+    assert np.array_equal(g.get_state(), before[0]) and np.array_equal(g.get_covariance(), before[1])

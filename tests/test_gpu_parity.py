@@ -492,3 +492,75 @@ def test_wide_p_nan_guard_inside_a_group(N, f_bad):
     assert np.abs(Pa[fin] - Pb[fin]).max() <= 1e-9 * np.abs(Pb[fin]).max()
     dx_ = np.abs(xa - xb)
     assert dx_.max() <= 1e-9 * np.abs(xb).max(), (np.argwhere(dx_ > 1e-10)[:12].tolist(), dx_.max())
+
+
+# (family, N, kernel, resident instance forced by index or -1, what describe() names)
+NAN_FAMILIES = [("resident_7_3", 50, 0, 6, "k_step_resident<7,3>"),          # the headline instance (forced: B = 3 < CU count)
+                ("resident_1_7", 12, 0, -1, "k_step_resident<1,7>"),         # one workgroup per CU, a small filter
+                ("hbm", 40, 1, -1, "P in HBM/L2"),                           # the HBM-path family
+                ("wide", 100, 0, -1, "k_update_feat_panelsvc")]              # wide P, the grouped look-ahead update
+
+
+@pytest.mark.parametrize("where", ["body", "bearing"])
+@pytest.mark.parametrize("family,N,kernel,inst,name", NAN_FAMILIES, ids=[f[0] for f in NAN_FAMILIES])
+def test_nan_in_P_against_the_structured_oracle(family, N, kernel, inst, name, where):
+    """A NaN already in P (put there with set_state, symmetrically): off every measured column (a body row x a body column) or
+    in one feature's bearing column.  The kernels form the gain from the measured feature's two columns of P only, so they skip
+    only the updates whose own columns hold the NaN (vi_ekf_meas.cpp:247 on their block-sparse gain); the reference's dense
+    P H^T (:241-247) turns the NaN into a NaN gain for EVERY update (0 x NaN).  The poisoned filter is compared with the
+    block-sparse oracle (vo_update_feat_structured) from the same start state -- codes, x, the finite part of P and the NaN
+    masks exactly --, the dense oracle is checked to differ (the deviation is kept on purpose: DESIGN.md §3), and the other
+    filters of the batch with the dense oracle."""
+    from vi_ekf_amd import capi
+    B, bad = 3, 1
+    sc = scene.make_scene(B, N, 1, seed=1300 + N)
+    g = v.BatchVIEKF(B, N, sc["params"])
+    if kernel:
+        g.set_kernel(kernel)
+    if inst >= 0:
+        g.set_tuning(capi.TUNE_RES_INSTANCE, inst)
+    for i in range(N):
+        assert (g.init_feature(sc["pix"][:, i, :].copy(), np.full(B, np.nan)) == 1).all()
+    assert name in g.describe(), g.describe()
+    if family.startswith("resident"):
+        assert g.describe().startswith(name), g.describe()
+    g.propagate(sc["u"][0], sc["dt"])
+    P = g.get_covariance()
+    f_bad = N // 3
+    r, c = (5, 12) if where == "body" else (5, 16 + 3 * f_bad)
+    P[bad, r, c] = P[bad, c, r] = np.nan
+    g.set_state(P=P)
+    x0, P0 = g.get_state(), g.get_covariance()
+    assert np.isnan(P0[bad]).sum() == 2 and np.isfinite(P0[[0, 2]]).all()
+
+    def oracle(b):
+        f = orc.OracleFilter(N).init(**oracle_params(sc["params"]))
+        for i in range(N):
+            f.init_feature(sc["pix"][b, i], i, float("nan"))
+        f.x[:] = x0[b]
+        f.P[:] = P0[b]
+        return f
+
+    res = g.update_feat(sc["z"][0], sc["slot"], sc["R"])
+    x, P1, st = g.get_state(), g.get_covariance(), g.get_status()
+    fs, fd = oracle(bad), oracle(bad)
+    for m in range(N):
+        sl = int(sc["slot"][bad, m])
+        assert res[bad, m] == fs.update_feat_structured(sc["z"][0, bad, m], sc["R"], sl), "code of update %d" % m
+        fd.update(orc.FEAT, sc["z"][0, bad, m], sc["R"], True, sl)
+    for got, ref, what in ((x[bad], fs.x, "x"), (P1[bad], fs.P, "P")):
+        assert (np.isnan(got) == np.isnan(ref)).all(), "NaN pattern of %s differs from the block-sparse oracle's" % what
+        fin = ~np.isnan(ref)
+        assert_close(got[fin], ref[fin], "%s of the poisoned filter (finite part)" % what)
+    assert np.isnan(P1[bad]).sum() == 2 and np.isfinite(x[bad]).all()
+    # the dense oracle differs: it skipped every update, the kernels (and the block-sparse form) applied the others
+    assert np.abs(fd.x - fs.x).max() > 1e-6 * np.abs(fs.x).max()
+    assert np.abs(x[bad] - x0[bad]).max() > 1e-6 * np.abs(x0[bad]).max()
+    # VIEKF_FLAG_NAN (NaNsInTheHouse, vi_ekf_error.cpp:6-18) on the poisoned filter only
+    assert st[bad] & capi.FLAG_NAN and not (st[[0, 2]] & capi.FLAG_NAN).any(), st
+    for b in (0, 2):
+        f = oracle(b)
+        for m in range(N):
+            assert res[b, m] == f.update(orc.FEAT, sc["z"][0, b, m], sc["R"], True, int(sc["slot"][b, m]))
+        assert_close(x[b], f.x, "x of filter %d" % b)
+        assert_close(P1[b], f.P, "P of filter %d" % b)

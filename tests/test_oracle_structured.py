@@ -50,3 +50,69 @@ def test_structured_gates_like_dense():
     rs = orc.run_steps_mt(fs, 1, u, float(sc["dt"][0]), z, sc["slot"], sc["R"], structured=True)
     assert rd[0, 0, 2] == orc.MEAS_GATED and (rd == rs).all()
     assert np.abs(fd[0].P - fs[0].P).max() <= 1e-11 * np.abs(fd[0].P).max()
+
+
+def _propagated(N, seed):
+    sc = scene.make_scene(1, N, 2, seed=seed)
+    f = _filters(sc, 1, N, N)[0]
+    f.propagate(sc["u"][0, 0], sc["dt"][0])
+    f.propagate(sc["u"][1, 0], sc["dt"][0])
+    return sc, f
+
+
+@pytest.mark.parametrize("N,over", [(6, {}), (12, dict(use_partial_update=0)), (50, {})])
+def test_update_feat_structured_equals_dense_update(N, over):
+    """OracleFilter.update_feat_structured, one update at a time, against the dense update(FEAT, ...) on finite P: same code,
+    x and P equal to rounding after every update (one pixel moved far enough to be gated)"""
+    sc = scene.make_scene(1, N, 2, seed=700 + N, params=over)
+    fd = _filters(sc, 1, N, N)[0]
+    fd.propagate(sc["u"][0, 0], sc["dt"][0])
+    fs = fd.clone()
+    z = sc["z"][1, 0].copy()
+    z[N // 2] += 300.0
+    codes = []
+    for m in range(N):
+        sl = int(sc["slot"][0, m])
+        rd = fd.update(orc.FEAT, z[m], sc["R"], True, sl)
+        rs = fs.update_feat_structured(z[m], sc["R"], sl)
+        codes.append(rd)
+        assert rd == rs, (m, rd, rs)
+        assert np.abs(fd.x - fs.x).max() <= 1e-11 * np.abs(fd.x).max(), m
+        assert np.abs(fd.P - fs.P).max() <= 1e-11 * np.abs(fd.P).max(), m
+    assert orc.MEAS_GATED in codes and orc.MEAS_SUCCESS in codes
+    with pytest.raises(ValueError):
+        fs.update_feat_structured(z[0], sc["R"], N + 3)
+
+
+@pytest.mark.parametrize("where", ["body", "bearing"])
+def test_nan_in_P_structured_and_dense_differ(where):
+    """The deviation the GPU kernels keep: a NaN in P reaches the dense gain P H^T through 0 x NaN from ANY
+    column of its row, so the dense update skips every later update (vi_ekf_meas.cpp:247); the block-sparse form reads only
+    the measured feature's two columns and skips only the update whose own columns hold it.  Neither spreads the NaN."""
+    N = 8
+    sc, fd = _propagated(N, 31)
+    P = fd.P
+    r, c = (5, 12) if where == "body" else (5, 16 + 3 * 3)        # body row x body column / x feature 3's first bearing column
+    P[r, c] = P[c, r] = np.nan
+    fs = fd.clone()
+    x0 = fd.x.copy()
+    z = sc["z"][1, 0]
+    for m in range(N):
+        sl = int(sc["slot"][0, m])
+        assert fd.update(orc.FEAT, z[m], sc["R"], True, sl) == orc.MEAS_SUCCESS
+        assert fs.update_feat_structured(z[m], sc["R"], sl) == orc.MEAS_SUCCESS
+    mask = np.zeros_like(P, dtype=bool)
+    mask[r, c] = mask[c, r] = True
+    for f in (fd, fs):
+        assert (np.isnan(f.P) == mask).all() and np.isfinite(f.x).all()
+        assert f.nans_in_the_house()
+    assert np.array_equal(fd.x, x0)                                # dense: every update skipped (fix_depth changes nothing here)
+    assert np.abs(fs.x - x0).max() > 1e-6                          # structured: the others applied
+    if where == "bearing":                                         # ... all but feature 3's: its own update is skipped
+        ref = fd.clone()
+        ref.P[r, c] = ref.P[c, r] = 0.0
+        for m in range(N):
+            sl = int(sc["slot"][0, m])
+            if sl != 3:
+                ref.update_feat_structured(z[m], sc["R"], sl)
+        assert np.abs(ref.x - fs.x).max() <= 1e-11 * np.abs(fs.x).max()

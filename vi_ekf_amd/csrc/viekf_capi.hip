@@ -1059,15 +1059,16 @@ int viekf_batch_set_state(viekf_batch* b, const double* x, const double* P, cons
                              (size_t)b->B * b->n, kind, b->stream));
   if (b->per_filter && (x || P))
     if (int rc = gather_scatter_home(b, 0)) return rc;
+  if (len_features) HIP_TRY(hipMemcpyAsync(b->d_len, len_features, sizeof(int32_t) * b->B, kind, b->stream));
   if (P) {
-    // the kernels keep P exactly symmetric and rely on it (their rank-2 update equals the reference's Joseph form only then)
+    // the kernels keep P exactly symmetric and rely on it (their rank-2 update equals the reference's Joseph form only then);
+    // a NaN in the active block (the new feature counts) raises VIEKF_FLAG_NAN
     StreamArgs a = make_args(b);
     const long tot = (long)b->n * b->n;
     hipLaunchKernelGGL(k_symmetrize, dim3((unsigned)((tot + 255) / 256), b->B), dim3(256), 0, b->stream, a);
     HIP_TRY(hipGetLastError());
     b->upper_stale = 0;
   }
-  if (len_features) HIP_TRY(hipMemcpyAsync(b->d_len, len_features, sizeof(int32_t) * b->B, kind, b->stream));
   if (where == VIEKF_HOST) HIP_TRY(hipStreamSynchronize(b->stream));
   return VIEKF_OK;
 }
@@ -1666,6 +1667,10 @@ int viekf_batch_propagate_filters_to(viekf_batch* b, const double* u, const doub
   if (int rc = check_batch(b)) return rc;
   if (!u || !dt || !dst_slot) return fail(VIEKF_ERR_INVALID, "u, dt and dst_slot must not be null");
   if (!b->per_filter) return fail(VIEKF_ERR_INVALID, "viekf_batch_select_filters first");
+  // (the launch runs under a mask of its own, dst_slot[b] >= 0: a caller's mask would be ignored and a filter it masked out
+  //  stepped anyway -- refused like viekf_batch_propagate_to)
+  if (b->active_on)
+    return fail(VIEKF_ERR_INVALID, "viekf_batch_propagate_filters_to under a participation mask (viekf_batch_set_active(NULL) first; dst_slot < 0 skips a filter)");
   bool any = false;
   for (int i = 0; i < b->B; i++) {
     if (dst_slot[i] >= b->hist_depth) return fail(VIEKF_ERR_INVALID, "ring slot out of range");

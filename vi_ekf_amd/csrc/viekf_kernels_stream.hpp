@@ -1117,18 +1117,22 @@ __global__ void k_eval_h(StreamArgs a, int type, const int* __restrict__ slot_al
 #endif
 
 // P <- (P + P^T) / 2 of every filter (a covariance handed in through viekf_batch_set_state): the kernels keep P exactly
-// symmetric from then on and rely on it
+// symmetric from then on and rely on it.  A NaN in the active block of the P handed in raises VIEKF_FLAG_NAN: the kernels only
+// test x for NaN, and the reference's NaNsInTheHouse (vi_ekf_error.cpp:6-18) tests P as well.
 #ifndef VIEKF_INSTANCES_ONLY
 __global__ void k_symmetrize(StreamArgs a) {
   const int b = blockIdx.y;
   const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= a.B || e >= (long)a.n * a.n) return;
   const int i = (int)(e % a.n), j = (int)(e / a.n);
-  if (i <= j) return;
+  if (i < j) return;
   double* P = a.P + a.si(b) * a.n * a.ld;
-  const double v = 0.5 * (P[i + (long)j * a.ld] + P[j + (long)i * a.ld]);
-  P[i + (long)j * a.ld] = v;
-  P[j + (long)i * a.ld] = v;
+  const double v = i == j ? P[i + (long)i * a.ld] : 0.5 * (P[i + (long)j * a.ld] + P[j + (long)i * a.ld]);
+  if (i > j) {
+    P[i + (long)j * a.ld] = v;
+    P[j + (long)i * a.ld] = v;
+  }
+  if (v != v && i < dxZ + 3 * a.len[b]) atomicOr(&a.flags[b], FLAG_NAN);
 }
 #endif
 
