@@ -2,7 +2,7 @@
 may be driven from different host threads (the reference's contract is one mutex per filter object, include/vi_ekf_ros.h:65).
 
 Two host threads create and step two batches that resolve to the SAME kernel instance with different feature counts (so both
-raise that instance's dynamic-LDS attribute -- the per-device high-water marks of viekf_capi.hip), 50 steps each, at the same
+raise that instance's dynamic-LDS attribute -- the per-device high-water marks of viekf_dispatch.hpp: raise_dyn_lds), 50 steps each, at the same
 time; both must equal their single-threaded runs bit for bit.  ctypes releases the GIL for the duration of every C call.
 """
 import threading

@@ -1,4 +1,4 @@
-"""Host-side invariants of the fused-step kernel's block ownership map (vi_ekf_amd/csrc/viekf_capi.hip: build_resmap).
+"""Host-side invariants of the fused-step kernel's block ownership map (vi_ekf_amd/csrc/viekf_resmap.cpp: build_resmap).
 
 The kernel keeps one 3x3 block of each symmetric pair {I, J} of feature blocks of P (vi_ekf.cpp:302-304 acts on all of P; the
 mirror is implied) in a register slot of one worker thread; which one is a table the host builds.  A wrong table would drop
@@ -12,8 +12,19 @@ import pytest
 
 from vi_ekf_amd import capi
 
-# (RB, NW, n_min, n_max) of kResInst in viekf_capi.hip
-INSTANCES = [(2, 1, 1, 15), (2, 2, 1, 22), (3, 2, 1, 25), (1, 7, 1, 29), (2, 7, 30, 41), (4, 3, 26, 38), (5, 3, 39, 43), (6, 3, 44, 47), (7, 3, 26, 50), (3, 7, 1, 50), (5, 6, 51, 57), (6, 6, 51, 67), (7, 6, 65, 72), (8, 6, 73, 77)]
+
+def instances():
+    """(RB, NW, n_min, n_max) of every row of the library's own dispatch table (viekf_instance_rows.hpp), in its order"""
+    fn = capi.lib().viekf_debug_res_instance
+    fn.argtypes = [C.c_int] + [C.POINTER(C.c_int)] * 4
+    fn.restype = C.c_int
+    rows, v = [], [C.c_int() for _ in range(4)]
+    while fn(len(rows), *[C.byref(x) for x in v]) == 0:
+        rows.append(tuple(x.value for x in v))
+    return rows
+
+
+INSTANCES = instances()
 
 
 def build(n, rb, nw):
@@ -24,6 +35,10 @@ def build(n, rb, nw):
     out = np.full(rb * 64 * nw, -1, dtype=np.int32)
     rc = fn(n, rb, nw, C.c_void_p(out.ctypes.data))
     return rc, out.reshape(rb, 64 * nw)
+
+
+def test_library_reports_its_fourteen_rows():
+    assert len(INSTANCES) == 14 and len(set(INSTANCES)) == 14
 
 
 @pytest.mark.parametrize("rb,nw,n_min,n_max", INSTANCES)

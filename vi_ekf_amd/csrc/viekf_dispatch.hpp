@@ -1,0 +1,294 @@
+// viekf_dispatch.hpp -- which kernel runs a batch and how it is launched: the instance tables, the choice of an instance when a
+// batch is created (setup_resident / setup_tiles), the launches of the three families.  Included by viekf_capi.hip ONLY: the
+// kernel headers below define non-template __global__ functions, a second includer would define them twice.
+#pragma once
+#include <cstdlib>
+#include <initializer_list>
+#include <mutex>
+
+#include "viekf_batch.hpp"
+#include "viekf_instances.hpp"
+#include "viekf_kernels_hooks.hpp"
+#include "viekf_kernels_wide.hpp"
+
+// (the fused-step kernels are compiled in viekf_inst.hip, one object file per group of instances)
+#define RES_EXT(...) VIEKF_RES_FLAVOURS(extern, __VA_ARGS__)
+#define TILE_EXT(...) VIEKF_TILE_FLAVOURS(extern, __VA_ARGS__)
+VIEKF_RES_LIST(RES_EXT)
+VIEKF_TILE_LIST(TILE_EXT)
+#undef RES_EXT
+#undef TILE_EXT
+
+namespace {
+
+constexpr int kThreads = 256;
+
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) belongs to a device's copy of a kernel and is shared by every batch (and
+// every host thread) that launches it: a high-water mark per device (`have`, a slot of the caller's static table), raised
+// under this lock and never lowered -- a second batch with fewer features must not take the first one's LDS away.
+std::mutex g_attr_mutex;
+template <typename Kernel>
+int raise_dyn_lds(std::initializer_list<Kernel*> kernels, size_t bytes, size_t& have) {
+  std::lock_guard<std::mutex> lk(g_attr_mutex);
+  if (bytes <= have) return VIEKF_OK;
+  for (Kernel* k : kernels)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  have = bytes;
+  return VIEKF_OK;
+}
+
+// elements and strides of the measurement noise R: r_mode 0 one R for all, 1 one per filter, 2 one per filter and measurement
+size_t r_count(const viekf_batch* b, int M, int r_mode) {
+  return r_mode == 0 ? 4 : (r_mode == 1 ? 4 * (size_t)b->B : 4 * (size_t)b->B * M);
+}
+void r_strides(int r_mode, int M, long* rsb, long* rsm) {
+  *rsb = r_mode == 1 ? 4 : (r_mode == 2 ? 4L * M : 0);
+  *rsm = r_mode == 2 ? 4 : 0;
+}
+
+size_t lds_propagate(const viekf_batch* b) {
+  return sizeof(double) * (size_t)(b->nxs + 256 + 96 + 256 + 256 + 96 + 256 + 256 + 16) + sizeof(BodyCtx) + 16;
+}
+size_t lds_update(const viekf_batch* b) { return sizeof(double) * (size_t)(b->nxs + 5 * b->n + 32); }
+
+// A grouped update (k_update_feat_blocked) keeps only the lower triangle of P current; the matrix-core propagate reads only
+// that and rewrites all of P.  Everything else reads P whole: mirror the lower triangle up first.
+int ensure_full_P(viekf_batch* b, int tolerate = 0) {
+  if (b->upper_stale <= tolerate) return VIEKF_OK;
+  StreamArgs a = make_args(b);
+  const int nt = (b->n + 31) / 32;
+  hipLaunchKernelGGL(k_mirror_upper, dim3((unsigned)(nt * (nt + 1) / 2), b->B), dim3(256), 0, b->stream, a);
+  HIP_TRY(hipGetLastError());
+  b->upper_stale = 0;
+  return VIEKF_OK;
+}
+// ... for the entry points that read all of P, ahead of their argument checks
+int need_full_P(viekf_batch* b) {
+  if (!b->upper_stale) return VIEKF_OK;
+  HIP_TRY(hipSetDevice(b->device));
+  return ensure_full_P(b);
+}
+
+// (VIEKF_TUNE_STREAM_MFMA = 0 keeps the kernels without matrix-core passes: experiments)
+bool stream_mfma_ok(const viekf_batch* b) { return b->tune_stream_mfma != 0; }
+
+int launch_propagate(viekf_batch* b, const double* d_u, const double* d_dt) {
+  if (int rc = ensure_full_P(b, stream_mfma_ok(b) ? 2 : 0)) return rc;
+  StreamArgs a = make_args(b);
+  if (stream_mfma_ok(b)) {   // feature/feature part on the fp64 matrix cores: reads and writes the lower triangle only
+    const size_t wlds = sizeof(double) * (size_t)WideLds(b->N, b->nxs).total;
+    if (b->tune_stream_mfma != 2 && 3 * b->N <= 512 && wlds <= 158 * 1024) {   // the K = 24 record form, records in LDS
+      static size_t have[64] = {};
+      if (int rc = raise_dyn_lds({&k_propagate_wide<512>}, wlds, have[b->device & 63])) return rc;
+      hipLaunchKernelGGL((k_propagate_wide<512>), dim3(b->B), dim3(512), wlds, b->stream, a, d_u, d_dt);
+    } else {                                                                    // r02's K = 38 form, operands staged in global scratch
+      hipLaunchKernelGGL((k_propagate_stream<512, true>), dim3(b->B), dim3(512), lds_propagate(b) + sizeof(double) * (9 * (size_t)b->N + 2),
+                         b->stream, a, d_u, d_dt);
+    }
+    b->upper_stale = 2;
+    b->stale_ever = 2;
+  } else
+    hipLaunchKernelGGL((k_propagate_stream<kThreads, false>), dim3(b->B), dim3(kThreads), lds_propagate(b), b->stream, a, d_u,
+                       d_dt);
+  HIP_TRY(hipGetLastError());
+  return VIEKF_OK;
+}
+
+// Group size of the grouped update (k_update_feat_blocked): the largest of 32 / 24 / 16 whose panel fits the LDS (fewer passes
+// over P for the narrower filters); 0 = the grouped kernel does not apply (then one pass per measurement).
+// (measured: at N = 64 groups of 32 are SLOWER than 16 -- 1.96 vs 1.83 ms per step, the sequential panel phase grows with the
+//  group -- while N = 100 gains 4 % from 24: the wider groups only where the passes dominate)
+// the look-ahead form of the grouped update (k_update_feat_panelsvc): groups of 16 -- the 48 rows of a group's features fit the
+// serving wave -- where its double-buffered LDS layout fits next to the panel (N <= 154 at groups of 16)
+bool panel_svc(const viekf_batch* b) {
+  if (b->tune_panel_svc == 0 || !(b->tune_block_group == 0 || b->tune_block_group == 16) || b->n > 512) return false;
+  const PsvLds PL(b->N, b->n, b->nxs, 16);
+  return sizeof(double) * (size_t)PL.total + 1024 <= 160 * 1024;
+}
+
+int blocked_group(const viekf_batch* b, size_t* lds_bytes) {
+  if (!stream_mfma_ok(b) || b->n > 512) return 0;
+  if (panel_svc(b)) {
+    if (lds_bytes) *lds_bytes = sizeof(double) * (size_t)PsvLds(b->N, b->n, b->nxs, 16).total;
+    return 16;
+  }
+  auto fits = [&](int cand, size_t* bytes) {
+    const BlkLds BL(b->N, b->n, b->nxs, cand);
+    *bytes = sizeof(double) * (size_t)BL.total;
+    return *bytes + 1024 <= 160 * 1024;   // (+ the kernel's small static LDS)
+  };
+  size_t bytes = 0;
+  if (b->tune_block_group && fits(b->tune_block_group, &bytes)) { if (lds_bytes) *lds_bytes = bytes; return b->tune_block_group; }
+  for (int cand : {32, 24, 16}) {
+    if (cand > 16 && b->n <= 256) continue;
+    if (fits(cand, &bytes)) { if (lds_bytes) *lds_bytes = bytes; return cand; }
+  }
+  return 0;
+}
+
+int launch_update(viekf_batch* b, const double* d_z, const int* d_slot, int M, const double* d_R, int r_mode,
+                  int* d_res) {
+  StreamArgs a = make_args(b);
+  long rsb = 0, rsm = 0;
+  r_strides(r_mode, M, &rsb, &rsm);
+  // wide P, several measurements: the blocked kernel (one HBM pass over P per group of BG measurements, fp64 MFMA pass)
+  size_t blds = 0;
+  const int bg = blocked_group(b, &blds);
+  if (M >= 1 && bg > 0) {   // (a single measurement too: a group of one, no mirror pass before it)
+    typedef void (*blk_kernel_t)(StreamArgs, const double*, const int*, int, const double*, long, long, int*);
+    const bool sv = panel_svc(b);
+    const blk_kernel_t kern = sv ? k_update_feat_panelsvc<512, 16>
+                                 : (bg == 32 ? k_update_feat_blocked<512, 32> : (bg == 24 ? k_update_feat_blocked<512, 24> : k_update_feat_blocked<512, 16>));
+    static size_t have[64][6] = {};
+    if (int rc = raise_dyn_lds({kern}, blds, have[b->device & 63][(bg == 32 ? 2 : (bg == 24 ? 1 : 0)) + (sv ? 3 : 0)])) return rc;
+    hipLaunchKernelGGL(kern, dim3(b->B), dim3(512), blds, b->stream, a, d_z, d_slot, M, d_R, rsb, rsm, d_res);
+    b->upper_stale = 2;   // (reads and writes the lower triangle only)
+    b->stale_ever = 2;
+  } else {
+    if (int rc = ensure_full_P(b)) return rc;   // (the one-measurement kernel reads whole columns)
+    hipLaunchKernelGGL(k_update_feat_stream<kThreads>, dim3(b->B), dim3(kThreads), lds_update(b), b->stream, a, d_z,
+                       d_slot, M, d_R, rsb, rsm, d_res);
+  }
+  HIP_TRY(hipGetLastError());
+  return VIEKF_OK;
+}
+
+typedef void (*res_kernel_t)(StreamArgs, int, const double*, const double*, const double*, const int*, int, int,
+                             const double*, long, long, int*);
+// The kernels behind the rows of kResInst / kTileInst (viekf_instance_rows.hpp), expanded from the same lists.
+// multi: several propagates per launch (viekf_batch_step_n); zu: the unit-Lambda instances (both flavours: step_n must stay
+// bit for bit what K propagates and a step give)
+struct ResKernels { res_kernel_t k[4]; };    // [multi + 2 * zu]
+struct TileKernels { res_kernel_t k[2]; };   // [multi]
+#define RES_KERNELS(RB, NW, NS, ...)                                                                   \
+  {{k_step_resident<RB, NW, false, NS, false>, k_step_resident<RB, NW, true, NS, false>,              \
+    k_step_resident<RB, NW, false, NS, true>, k_step_resident<RB, NW, true, NS, true>}},
+#define TILE_KERNELS(NT, NW, ...) \
+  {{k_step_tiles_pair<NT, false>, k_step_tiles_pair<NT, true>}}, {{k_step_tiles<NT, NW, false>, k_step_tiles<NT, NW, true>}},
+const ResKernels kResKernels[] = {VIEKF_RES_LIST(RES_KERNELS)};
+const TileKernels kTileKernels[] = {VIEKF_TILE_LIST(TILE_KERNELS)};
+#undef RES_KERNELS
+#undef TILE_KERNELS
+static_assert(sizeof(kResKernels) / sizeof(kResKernels[0]) == kNumResInst, "one set of kernels per row of kResInst");
+static_assert(sizeof(kTileKernels) / sizeof(kTileKernels[0]) == kNumTileInst, "one set of kernels per row of kTileInst");
+
+res_kernel_t res_kernel(int inst, bool multi, bool zu) { return kResKernels[inst].k[(multi ? 1 : 0) + (zu ? 2 : 0)]; }
+res_kernel_t tile_kernel(int inst, bool multi) { return kTileKernels[inst].k[multi ? 1 : 0]; }
+
+int setup_tiles(viekf_batch* b) {
+  b->tile_inst = -1;
+  if (!b->tune_tiles || b->N + 14 > 64 || b->N < 1) return VIEKF_OK;
+  const int NT = 1 + (b->N + 4) / 5;
+  int cus = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->device) != hipSuccess || cus <= 0) cus = 256;
+  for (int i = 0; i < kNumTileInst; i++) {
+    const TileInst& r = kTileInst[i];
+    if (r.NT != NT || 16 * NT > 64 * r.NW) continue;   // (one worker thread per tile-space row brings the next column pair up to date)
+    // tune_tiles: 0 / 1 the resident family (on the MI355X it is the faster one at every batch size measured, so "automatic"
+    // never picks a tile instance), 2 the single form, 3 the paired form -- whatever the batch size
+    if (b->tune_tiles == 1) continue;
+    if (b->tune_tiles == 2 && r.pair) continue;
+    if (b->tune_tiles == 3 && !r.pair) continue;
+    const TileLds L(b->N, b->n, b->nxs);
+    const size_t lds = sizeof(double) * (size_t)L.total * (r.pair ? 2 : 1);
+    if (lds > (size_t)r.max_lds_kb * 1024) continue;
+    static size_t have[64][kNumTileInst] = {};
+    const res_kernel_t* k = kTileKernels[i].k;
+    if (int rc = raise_dyn_lds({k[0], k[1]}, lds, have[b->device & 63][i])) return rc;
+    b->tile_inst = i; b->tile_lds = lds;
+    break;
+  }
+  return VIEKF_OK;
+}
+
+int setup_resident(viekf_batch* b) {
+  b->res_inst = -1;
+  const bool force = b->tune_res_inst >= 0;   // (VIEKF_TUNE_RES_INSTANCE: pick an instance by index)
+  for (int i = 0; i < kNumResInst; i++) {
+    const ResInst& r = kResInst[i];
+    if (force && b->tune_res_inst != i) continue;
+    if (b->N < r.nmin || b->N > r.nmax) continue;
+    if (b->N * (b->N + 1) / 2 > r.RB * r.NW * 64 || b->N > r.NW * 64) continue;
+    const ResLds L(b->N, b->n, b->nxs);
+    const size_t lds = sizeof(double) * (size_t)L.total;
+    if (lds > (size_t)r.max_lds_kb * 1024) continue;
+    if (r.max_lds_kb <= 80 && !force) {   // two small workgroups per CU only pay when the batch fills the CUs more than once
+      int cus = 0;
+      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->device) != hipSuccess || cus <= 0) cus = 256;
+      if (b->B <= cus) continue;
+      if (r.max_lds_kb <= 40 && b->B <= 2 * cus) continue;   // (four per CU: only when two per CU would leave filters waiting)
+    }
+    std::vector<int> map;
+    if (!build_resmap(b->N, r.RB, r.NW, map)) continue;
+    if (b->d_resmap) { HIP_TRY(hipFree(b->d_resmap)); b->d_resmap = nullptr; }
+    HIP_TRY(hipMalloc(&b->d_resmap, sizeof(int) * map.size()));
+    HIP_TRY(hipMemcpy(b->d_resmap, map.data(), sizeof(int) * map.size(), hipMemcpyHostToDevice));
+    static size_t have[64][kNumResInst] = {};
+    const res_kernel_t* k = kResKernels[i].k;
+    if (int rc = raise_dyn_lds({k[0], k[1], k[2], k[3]}, lds, have[b->device & 63][i])) return rc;
+    b->res_inst = i; b->res_lds = lds;
+    break;
+  }
+  return VIEKF_OK;
+}
+
+// Timing-only ablation (results become wrong) exists in a -DVIEKF_ABLATE diagnostic build only (tools/build_variant.sh): the
+// bits 1 skip sweeps, 2 skip state correction, 4 skip the column extraction come from VIEKF_DEBUG_ABLATE there.  The product
+// library has no such switch.
+#ifdef VIEKF_ABLATE
+int dbg_bits() {
+  static const int v = []() { const char* e = getenv("VIEKF_DEBUG_ABLATE"); return e ? atoi(e) : 0; }();
+  return v;
+}
+#else
+constexpr int dbg_bits() { return 0; }
+#endif
+
+bool use_tiles(const viekf_batch* b) { return b->tile_inst >= 0 && b->family != 1; }
+bool use_resident(const viekf_batch* b) { return (b->res_inst >= 0 || b->tile_inst >= 0) && b->family != 1; }
+
+// one launch handles at most res_mcap(N) measurements; longer lists are chunked (P makes one extra HBM round trip per chunk)
+int launch_resident(viekf_batch* b, bool do_prop, const double* d_u, const double* d_dt, const double* d_z,
+                    const int* d_slot, int M, const double* d_R, int r_mode, int* d_res, double* x_out = nullptr,
+                    double* P_out = nullptr, int KP = 1, const int* smap_out = nullptr) {
+  // (the fused kernel loads the lower triangle only and stores the lower triangle only: no symmetrisation before or after)
+  StreamArgs a = make_args(b);
+  if (x_out) { a.x_out = x_out; a.P_out = P_out; }   // (only meaningful for a single-chunk launch)
+  a.smap_out = smap_out;
+  long rsb = 0, rsm = 0;
+  r_strides(r_mode, M, &rsb, &rsm);
+  const bool tiles = use_tiles(b);
+  const res_kernel_t kern = tiles ? tile_kernel(b->tile_inst, KP > 1) : res_kernel(b->res_inst, KP > 1, b->res_zu);
+  const bool pair = tiles && kTileInst[b->tile_inst].pair;
+  const int threads = tiles ? (pair ? 512 : (kTileInst[b->tile_inst].NW + 1) * 64) : (kResInst[b->res_inst].NW + kResInst[b->res_inst].NS) * 64;
+  const unsigned grid = pair ? (unsigned)((b->B + 1) / 2) : (unsigned)b->B;
+  const size_t lds = tiles ? b->tile_lds : b->res_lds;
+  int m0 = 0;
+  do {
+    const int cap = res_mcap(b->N);
+    const int mc = (M - m0 < cap) ? (M - m0) : cap;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, b->stream, a,
+                       ((do_prop && m0 == 0) ? (1 | (KP << 16)) : 0) | ((dbg_bits() & 0xff) << 8), d_u, d_dt, d_z ? d_z + 2L * m0 : nullptr,
+                       d_slot ? d_slot + m0 : nullptr, mc, M, d_R ? d_R + rsm * m0 : nullptr, rsb, rsm,
+                       d_res ? d_res + m0 : nullptr);
+    HIP_TRY(hipGetLastError());
+    m0 += mc;
+  } while (m0 < M);
+  b->upper_stale = 2;
+  b->stale_ever = 2;
+  return VIEKF_OK;
+}
+
+// per-filter mode: (x, P) of every filter between its live ring slot and the batch's own buffers (to_home != 0: ring -> home)
+int gather_scatter_home(viekf_batch* b, int to_home) {
+  if (!b->d_zero) {
+    HIP_TRY(hipMalloc(&b->d_zero, sizeof(int) * (size_t)b->B));
+    HIP_TRY(hipMemsetAsync(b->d_zero, 0, sizeof(int) * (size_t)b->B, b->stream));
+  }
+  StreamArgs a = make_args(b);
+  hipLaunchKernelGGL(k_ring_copy, dim3(b->B), dim3(256), 0, b->stream, a, b->home_x, b->home_P, b->d_zero, to_home, 1);
+  HIP_TRY(hipGetLastError());
+  return VIEKF_OK;
+}
+
+}  // namespace

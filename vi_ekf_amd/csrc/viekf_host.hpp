@@ -10,7 +10,9 @@ typedef std::map<std::string, std::string> YamlMap;
 bool yaml_parse_file(const std::string& path, YamlMap& out, std::string& err);
 bool yaml_get_doubles(const YamlMap& m, const std::string& key, double* out, int count, std::string& err);
 bool yaml_get_string(const YamlMap& m, const std::string& key, std::string& out, std::string& err);
-// records `msg` as this thread's viekf_last_error() and returns `code` (for the C-ABI files other than viekf_capi.hip)
+// records `msg` as this thread's viekf_last_error() and returns `code` (defined in viekf_capi.hip, used by every C-ABI file)
 int set_last_error(int code, const std::string& msg);
+// block ownership map [RB][64 * NWV] of the fused-step kernel (viekf_resmap.cpp); false when the blocks do not fit
+bool build_resmap(int N, int RB, int NWV, std::vector<int>& map, int* used_slots = nullptr);
 
 }  // namespace viekf

@@ -3,8 +3,8 @@
 #define VIEKF_INSTANCES_ONLY
 #include "viekf_instances.hpp"
 
-#define RES_DEF(RB, NW, NS) VIEKF_RES_FLAVOURS(, RB, NW, NS)
-#define TILE_DEF(NT, NW) VIEKF_TILE_FLAVOURS(, NT, NW)
+#define RES_DEF(...) VIEKF_RES_FLAVOURS(, __VA_ARGS__)
+#define TILE_DEF(...) VIEKF_TILE_FLAVOURS(, __VA_ARGS__)
 #if VIEKF_INST_GROUP == 0
 VIEKF_RES_LIST_0(RES_DEF)
 #elif VIEKF_INST_GROUP == 1

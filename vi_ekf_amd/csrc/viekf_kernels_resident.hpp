@@ -10,7 +10,7 @@
 //
 // Ownership: the 3N x 3N feature part of P is a grid of 3x3 blocks (I,J).  P is symmetric, so of every
 // unordered pair {I,J} only ONE block is kept (I >= J); which worker thread keeps it in which of its RB register slots is a
-// table built by the host (8 x 8 tiles of blocks per 64-lane group: build_resmap, viekf_capi.hip).  The 16 body columns
+// table built by the host (8 x 8 tiles of blocks per 64-lane group: build_resmap, viekf_resmap.cpp).  The 16 body columns
 // P[:,0:16] live in LDS for the whole step (the body rows are their mirror).  A rank-2 sweep needs K for the block's rows and
 // W for its columns; the propagation Phi P Phi^T + Gd Qu Gd^T is a register-tiled K = 24 contraction over one record per
 // row (viekf_resident_common.hpp).  lambda_feat is the same for every feature slot (vi_ekf.cpp:139-144), so the

@@ -107,7 +107,7 @@ __device__ __forceinline__ void res_worker(const StreamArgs& a, const ResShared&
   const int N = S.N, n = S.n, ld = a.ld, nf = S.nf, len = S.len;
   double* P = a.P + S.si * n * ld;
   // SYMMETRIC ownership: of each unordered pair of feature blocks {I,J} only one is kept (I >= J); which thread keeps it in
-  // which of its RB slots is a table built by the host (build_resmap, viekf_capi.hip: 8 x 8 tiles of blocks per (slot, wave)
+  // which of its RB slots is a table built by the host (build_resmap, viekf_resmap.cpp: 8 x 8 tiles of blocks per (slot, wave)
   // group, so that the column pair of one feature is published from few groups).  Slot a = 0 of the threads t < N is the
   // diagonal block (t, t).
   const int tid_ = tid;

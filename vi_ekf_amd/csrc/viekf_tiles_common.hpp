@@ -11,8 +11,8 @@
 // Row space.  P's rows are re-indexed so that no feature straddles a tile:  tile 0 = the 16 body rows,  tile t >= 1 = the
 // features 5 (t - 1) .. 5 (t - 1) + 4, three rows each, and one pad row (index 15: always zero).  q = 16 t + w  <->  P row
 // w (t = 0)  or  16 + 15 (t - 1) + w (t >= 1, w < 15).  NT = 1 + ceil(N / 5) tiles per side, NQ = 16 NT rows.
-// Ownership.  Only tiles (TI, TJ) with TI >= TJ are held (P is symmetric); tile -> (wave, slot) is a host-built table
-// (build_tilemap, viekf_capi.hip), wave = (TI + TJ) mod NW so that the NT tiles that hold one feature's rows / columns spread
+// Ownership.  Only tiles (TI, TJ) with TI >= TJ are held (P is symmetric); tile -> (wave, slot) is fixed at compile
+// time (viekf_tiles_worker.hpp), wave = (TI + TJ) mod NW so that the NT tiles that hold one feature's rows / columns spread
 // evenly over the waves.  A diagonal tile holds both triangles, but only its LOWER one (P row >= P column) is ever read back
 // (column extraction, store): P is exactly symmetric by construction, whatever the rounding of the two halves.
 // Register content of a tile (TI, TJ), lane l, register r (the instruction's C/D layout: row = (l >> 4) + 4 r, col = l & 15):
