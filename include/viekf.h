@@ -276,6 +276,26 @@ int viekf_batch_propagate_filters_to(viekf_batch *b, const double *u, const doub
  * steps run one by one, every slot is written and *intermediates_written = 1.  The final state is the same either way. */
 int viekf_batch_propagate_n_to(viekf_batch *b, int32_t K, const double *u, const double *dt, const int32_t *dst_slots,
                                int32_t *intermediates_written, viekf_mem where);
+/* The same replay for filters on INDEPENDENT clocks (src/vi_ekf/vi_ekf_meas.cpp:106-118 per filter, every step of it
+ * src/vi_ekf/vi_ekf.cpp:298-306): filter b takes k_count[b] propagates, 0 <= k_count[b] <= Kmax <= 64, with the inputs u[k][b],
+ * dt[k][b] for k < k_count[b] -- entries at k >= k_count[b] are never read -- from its live ring slot into dst_slot[b], which
+ * becomes its live slot.  k_count[b] == 0 or dst_slot[b] < 0: the filter is not touched.  u [Kmax][batch][6] and dt [Kmax][batch]
+ * as `where` says, k_count and dst_slot [batch] in HOST memory.  Needs viekf_batch_select_filters first.  Refused with
+ * VIEKF_ERR_INVALID, all of it checked before anything changes: a participation mask in force (viekf_batch_set_active; the call
+ * has its own, like propagate_filters_to), a destination that is the filter's live slot, a slot or a count out of range, and --
+ * whichever route is taken -- a ring of fewer than 3 slots when a filter takes more than one propagate.
+ * Resident fused kernel: ONE launch of its multi-propagate instance; every filter's P stays on chip through its own k_count[b]
+ * propagates and only dst_slot[b] is written: *intermediates_written = 0.  The result is bit for bit what k_count[b] calls of
+ * viekf_batch_propagate_filters_to give.  Everywhere else (the HBM-path family, the opt-in tile family) the steps run one by one
+ * through viekf_batch_propagate_filters_to, a filter's steps landing by turns in dst_slot[b] and in ONE SCRATCH SLOT, the last of
+ * them in dst_slot[b]: the scratch slot is the slot after dst_slot[b] in ring order, (dst_slot[b] + 1) % depth, or the one after
+ * that if this is the filter's live slot -- in a ring that is written in order, the oldest slot, the next to be overwritten
+ * anyway.  Its contents are lost where *intermediates_written = 1 (some filter's intermediate state was written); the slot the
+ * filter started from is never written.  The final state is the same either way. */
+int viekf_batch_propagate_n_filters_to(viekf_batch *b, int32_t Kmax, const double *u /* [Kmax][batch][6] */,
+                                       const double *dt /* [Kmax][batch] */, const int32_t *k_count /* [batch], host */,
+                                       const int32_t *dst_slot /* [batch], host */, int32_t *intermediates_written,
+                                       viekf_mem where);
 
 /* ONE measurement of any model of the reference's table per filter: VIEKF::update with
  * h_acc/h_alt/h_att/h_pos/h_vel/h_qzeta/h_feat/h_depth/h_inv_depth, src/vi_ekf/vi_ekf_meas.cpp:196-386.

@@ -273,6 +273,27 @@ class BatchVIEKF:
     def restore(self, slot):
         capi.check(capi.lib().viekf_batch_restore(self._h, int(slot)))
 
+    def select_filters(self, slot):
+        """per-filter live ring slots (viekf_batch_select_filters); slot [B] int32 on the host, < 0 = unchanged"""
+        sl = np.ascontiguousarray(slot, dtype=np.int32)
+        if sl.shape != (self.B,):
+            raise ValueError("expected shape %s, got %s" % ((self.B,), sl.shape))
+        capi.check(capi.lib().viekf_batch_select_filters(self._h, C.c_void_p(sl.ctypes.data)))
+
+    def propagate_n_filters_to(self, u, dt, k_count, dst_slot):
+        """filter b: k_count[b] propagates (u [K,B,6], dt [K,B]; rows k >= k_count[b] are not read) from its live ring slot into
+        dst_slot[b] (viekf_batch_propagate_n_filters_to) -> intermediates_written"""
+        self._keep = []
+        K = int(u.shape[0])
+        pu, w = self._arg(u, np.float64, (K, self.B, 6), None)
+        pdt, w = self._arg(dt, np.float64, (K, self.B), w)
+        pk, _ = self._arg(np.asarray(k_count), np.int32, (self.B,), None)
+        pd, _ = self._arg(np.asarray(dst_slot), np.int32, (self.B,), None)
+        iw = C.c_int32(-1)
+        capi.check(capi.lib().viekf_batch_propagate_n_filters_to(self._h, K, pu, pdt, pk, pd, C.byref(iw), w))
+        self._keep = []
+        return iw.value
+
     def step_n(self, u, dt, z, slot, R, result=None):
         """K propagates (u [K,B,6], dt [K,B]: the IMU samples since the last frame) + M feature updates in one launch"""
         self._keep = []

@@ -92,7 +92,8 @@ StreamArgs make_args(const viekf_batch* b) {
   StreamArgs a;
   a.smap = b->per_filter ? b->d_smap : nullptr;
   a.smap_out = nullptr;
-  a.x = b->d_x; a.P = b->d_P; a.len = b->d_len; a.flags = b->d_flags;
+  a.kcount = nullptr;
+  a.x =b->d_x; a.P = b->d_P; a.len = b->d_len; a.flags = b->d_flags;
   a.Qx = b->d_Qx; a.lambda = b->d_lambda; a.ws = b->d_ws;
   a.B = b->B; a.N = b->N; a.nx = b->nx; a.nxs = b->nxs; a.n = b->n; a.ld = b->ld;
   a.ws_stride = b->ws_stride;

@@ -908,6 +908,79 @@ int viekf_batch_propagate_filters_to(viekf_batch* b, const double* u, const doub
   return st.finish(true);
 }
 
+int viekf_batch_propagate_n_filters_to(viekf_batch* b, int32_t Kmax, const double* u, const double* dt, const int32_t* k_count,
+                                       const int32_t* dst_slot, int32_t* intermediates_written, viekf_mem where) {
+  if (int rc = check_batch(b)) return rc;
+  if (!u || !dt || !k_count || !dst_slot) return fail(VIEKF_ERR_INVALID, "u, dt, k_count and dst_slot must not be null");
+  if (Kmax < 1 || Kmax > 64) return fail(VIEKF_ERR_INVALID, "1 <= Kmax <= 64 propagates per call");
+  if (!b->per_filter) return fail(VIEKF_ERR_INVALID, "viekf_batch_select_filters first");
+  if (b->active_on)   // (the call runs under a mask of its own, like viekf_batch_propagate_filters_to)
+    return fail(VIEKF_ERR_INVALID, "viekf_batch_propagate_n_filters_to under a participation mask (viekf_batch_set_active(NULL) first; k_count 0 or dst_slot < 0 skips a filter)");
+  const size_t B = (size_t)b->B;
+  const int H = b->hist_depth;
+  // every check before anything changes: the steps below cannot be refused half way
+  int kmax = 0;
+  for (size_t i = 0; i < B; i++) {
+    if (k_count[i] < 0 || k_count[i] > Kmax) return fail(VIEKF_ERR_INVALID, "need 0 <= k_count[b] <= Kmax");
+    if (dst_slot[i] >= H) return fail(VIEKF_ERR_INVALID, "ring slot out of range");
+    if (k_count[i] == 0 || dst_slot[i] < 0) continue;
+    if (dst_slot[i] == b->live_slots[i]) return fail(VIEKF_ERR_INVALID, "a destination slot is the filter's live slot");
+    kmax = std::max(kmax, (int)k_count[i]);
+  }
+  if (kmax >= 2 && H < 3)   // (live slot, destination and the scratch slot of the step-by-step route: whichever route is taken)
+    return fail(VIEKF_ERR_INVALID, "several propagates per filter need a ring of at least 3 slots");
+  if (intermediates_written) *intermediates_written = 0;
+  if (kmax == 0) return VIEKF_OK;
+  HIP_TRY(hipSetDevice(b->device));
+  if (kmax >= 2 && use_resident(b) && !use_tiles(b)) {
+    // ONE launch of the fused kernel's multi-propagate instance: filter b is loaded from its live slot, P stays on chip through its
+    // own k_count[b] propagates and is stored into dst_slot[b] only
+    std::vector<unsigned char> act(B);
+    std::vector<int32_t> omap(B), kc(B);
+    for (size_t i = 0; i < B; i++) {
+      const bool on = k_count[i] > 0 && dst_slot[i] >= 0;
+      act[i] = on ? 1 : 0;
+      omap[i] = (on ? dst_slot[i] : b->live_slots[i]) * b->B + (int32_t)i;
+      kc[i] = on ? k_count[i] : 1;   // (a filter outside the mask never reads it)
+    }
+    const double *d_u = nullptr, *d_dt = nullptr;
+    const unsigned char* d_act = nullptr;
+    const int32_t *d_omap = nullptr, *d_kc = nullptr;
+    Staged st(b, where);
+    if (int rc = st.begin(in(u, 6 * B * (size_t)Kmax, &d_u), in(dt, B * (size_t)Kmax, &d_dt), in_host(act.data(), B, &d_act),
+                          in_host(omap.data(), B, &d_omap), in_host(kc.data(), B, &d_kc)))
+      return rc;
+    const bool saved_on = b->active_on;
+    unsigned char* saved_mask = b->d_active;
+    b->active_on = true; b->d_active = const_cast<unsigned char*>(d_act);
+    const int rc = launch_resident(b, true, d_u, d_dt, nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, kmax, d_omap, d_kc);
+    b->active_on = saved_on; b->d_active = saved_mask;
+    if (rc) return rc;
+    for (size_t i = 0; i < B; i++)   // (the launch is issued: the kernel moves the device's map entries itself)
+      if (act[i]) b->live_slots[i] = dst_slot[i];
+    return st.finish(true);
+  }
+  // Step by step (the HBM-path family, the tile family, one propagate per filter): step k of filter b goes into dst_slot[b] or
+  // into its scratch slot -- the slot after dst_slot[b] in ring order that is not its live slot -- by turns, the last one into
+  // dst_slot[b].  (viekf_batch_propagate_filters_to moves the host's live-slot mirror after each step it has issued.)
+  std::vector<int32_t> step(B), scratch(B, -1);
+  for (size_t i = 0; i < B; i++) {   // (fixed by the slot the filter starts from)
+    if (dst_slot[i] < 0 || k_count[i] < 2) continue;
+    scratch[i] = (dst_slot[i] + 1) % H;
+    if (scratch[i] == b->live_slots[i]) scratch[i] = (scratch[i] + 1) % H;
+  }
+  for (int k = 0; k < kmax; k++) {
+    for (size_t i = 0; i < B; i++) {
+      step[i] = -1;
+      if (dst_slot[i] < 0 || k >= k_count[i]) continue;
+      step[i] = ((k_count[i] - 1 - k) & 1) ? scratch[i] : dst_slot[i];
+    }
+    if (int rc = viekf_batch_propagate_filters_to(b, u + 6 * B * (size_t)k, dt + B * (size_t)k, step.data(), where)) return rc;
+    if (k + 1 < kmax && intermediates_written) *intermediates_written = 1;
+  }
+  return VIEKF_OK;
+}
+
 int viekf_batch_update(viekf_batch* b, int32_t type, const double* z, int32_t zdim, const double* R, int32_t rdim,
                        int32_t r_mode, const int32_t* slot, const uint8_t* active, int32_t* result, viekf_mem where) {
   if (int rc = check_batch(b)) return rc;

@@ -250,11 +250,12 @@ bool use_resident(const viekf_batch* b) { return (b->res_inst >= 0 || b->tile_in
 // one launch handles at most res_mcap(N) measurements; longer lists are chunked (P makes one extra HBM round trip per chunk)
 int launch_resident(viekf_batch* b, bool do_prop, const double* d_u, const double* d_dt, const double* d_z,
                     const int* d_slot, int M, const double* d_R, int r_mode, int* d_res, double* x_out = nullptr,
-                    double* P_out = nullptr, int KP = 1, const int* smap_out = nullptr) {
+                    double* P_out = nullptr, int KP = 1, const int* smap_out = nullptr, const int* kcount = nullptr) {
   // (the fused kernel loads the lower triangle only and stores the lower triangle only: no symmetrisation before or after)
   StreamArgs a = make_args(b);
   if (x_out) { a.x_out = x_out; a.P_out = P_out; }   // (only meaningful for a single-chunk launch)
   a.smap_out = smap_out;
+  a.kcount = kcount;   // (per-filter propagate counts: the resident multi-propagate instances, KP > 1, read them; KP is their maximum)
   long rsb = 0, rsm = 0;
   r_strides(r_mode, M, &rsb, &rsm);
   const bool tiles = use_tiles(b);

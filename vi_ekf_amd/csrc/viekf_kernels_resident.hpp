@@ -26,7 +26,10 @@ namespace viekf {
 
 // Common prologue of the fused-step kernels: LDS carve-up, state, lambdas, mailboxes and the measurement table (validity
 // decided once, here).  T = workgroup size.  Ends with the table barriers.
-template <int T>
+// MP (the multi-propagate instances): the trip count of the propagate loop, S.kp, is this filter's own where the launch carries
+// per-filter counts (StreamArgs::kcount); it is one value for the whole workgroup, read here ONCE -- the service wave and the
+// worker waves both loop to S.kp and meet at the same barriers.
+template <int T, bool MP>
 __device__ __forceinline__ void res_prologue(const StreamArgs& a, ResShared& S, double* smem, int do_prop,
                                              const double* __restrict__ dt_all, const double* __restrict__ z_all,
                                              const int* __restrict__ slot_all, int M, int m_stride,
@@ -44,6 +47,7 @@ __device__ __forceinline__ void res_prologue(const StreamArgs& a, ResShared& S, 
   S.ctx = reinterpret_cast<BodyCtx*>(smem + L.ctx);
   S.N = a.N; S.mcap = res_mcap(a.N); S.n = a.n; S.nf = 3 * a.N; S.len = a.len[b]; S.M = M; S.mstride = m_stride; S.do_prop = do_prop & 1; S.dbg = (do_prop >> 8) & 0xff; S.kp = (do_prop >> 16) > 0 ? (do_prop >> 16) : 1; S.B = a.B; S.b = b; S.stamps = a.ws;
   S.si = a.si(b); S.so = a.so(b);
+  if (MP && a.kcount) S.kp = a.kcount[b];
   {
     const double* xg = a.x + S.si * a.nxs;
     for (int i = tid; i < a.nxs; i += T) S.xs[i] = (i < xZ + 5 * S.len) ? xg[i] : 0.0;
@@ -109,7 +113,7 @@ __global__ __launch_bounds__((NW + NS) * 64, (NW <= 3) ? 2 : 1) void k_step_resi
   }
 #endif
   ResShared S;
-  res_prologue<T>(a, S, smem, do_prop, dt_all, z_all, slot_all, M, m_stride, R_all, r_stride_b, r_stride_m, result_all);
+  res_prologue<T, MP>(a, S, smem, do_prop, dt_all, z_all, slot_all, M, m_stride, R_all, r_stride_b, r_stride_m, result_all);
   // The service wave's chain is the floor of an update, so it should not share its SIMD's issue slots with a worker wave.  A
   // workgroup's waves go to the four SIMDs round-robin: with 7 waves (NW = 6, one service wave) the 4th one is alone on its
   // SIMD -- that is the service wave.  Otherwise the last wave(s) serve.

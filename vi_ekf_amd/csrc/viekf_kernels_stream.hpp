@@ -36,6 +36,9 @@ struct StreamArgs {
   // smap_out: where the fused kernel stores filter b's state (viekf_batch_propagate_filters_to: slot i_b -> slot i_b + 1, no copy).
   int* smap;            // (device memory; the fused kernel moves a filter's entry to smap_out[b] when it stores it there)
   const int* smap_out;
+  // [B] or NULL: propagates of THIS launch per filter (viekf_batch_propagate_n_filters_to; >= 1 for every filter that takes part).
+  // Read by the multi-propagate instances of the fused kernel only; NULL = the launch-wide count of the launch word.
+  const int* kcount;
   __device__ __forceinline__ long si(int b) const { return smap ? (long)smap[b] : (long)b; }
   __device__ __forceinline__ long so(int b) const { return smap_out ? (long)smap_out[b] : si(b); }
 };
