@@ -8,3 +8,5 @@ from .batch import BatchVIEKF  # noqa: F401
 from .capi import Params, ViekfError, device_count, load_yaml  # noqa: F401
 from .seq import SeqVIEKF  # noqa: E402,F401
 from .klt import KLTTracker, track_frame  # noqa: E402,F401
+from . import diag  # noqa: E402,F401
+from .diag import consistency, innovation  # noqa: E402,F401

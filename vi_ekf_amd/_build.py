@@ -11,6 +11,7 @@ def sources():
     out = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".cpp", ".hpp", "Makefile"))]
     out.append(os.path.join(os.path.dirname(HERE), "include", "viekf.h"))
     out.append(os.path.join(os.path.dirname(HERE), "include", "viekf_klt.h"))
+    out.append(os.path.join(os.path.dirname(HERE), "include", "viekf_diag.h"))
     return out
 
 

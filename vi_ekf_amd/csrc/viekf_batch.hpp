@@ -70,6 +70,10 @@ struct viekf_batch {
   int tune_block_group = 0;    // 16 / 24 / 32: group size of the grouped update where its panel fits
   int tune_stream_mfma = 1;    // 0: the streaming kernels without matrix-core passes
   int tune_panel_svc = 1;      // 0: the grouped update without the service wave (k_update_feat_blocked)
+  // viekf_diag_consistency where the packed triangle does not fit the LDS: allocated on first use, at most 256 MiB while one
+  // filter's triangle fits that (the batch is processed in chunks of filters)
+  double* d_diag_ws = nullptr;
+  size_t diag_ws_bytes = 0;
 };
 
 namespace {
