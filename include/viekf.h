@@ -137,10 +137,22 @@ int viekf_batch_set_kernel(viekf_batch *b, int32_t family);
  *                            service wave running it ahead of the others (k_update_feat_panelsvc)
  *   VIEKF_TUNE_TILES         the tile family of the fused step (P as fp64-MFMA accumulator tiles, N = 46..50): 0 / 1 = not used
  *                            (the default: the resident family measures faster on the MI355X at every batch size), 2 = its
- *                            one-filter-per-workgroup form, 3 = its paired form (two filters per workgroup) */
+ *                            one-filter-per-workgroup form, 3 = its paired form (two filters per workgroup)
+ *   VIEKF_TUNE_PACKED_P      1 (default) = the resident family keeps P PACKED between its launches: a fused launch stores the
+ *                            kernel's own register / LDS image into the filter's P (no conversion to the column-major matrix)
+ *                            and the next one loads it back; 0 = every fused launch stores canonical P.  Used only where the
+ *                            image fits the filter's n * ld doubles, the batch advances as a whole (no per-filter live slots,
+ *                            no participation mask) and the launch is not the tile family's; viekf_batch_describe says which
+ *                            form the batch stores.  Results are bit for bit the same either way.
+ * P in DEVICE MEMORY is therefore not the canonical matrix until a reader asks: after a fused launch the live P (and a ring
+ * slot written by one) may be packed, and in every case only its lower triangle is current.  Every entry point that reads or
+ * edits P (get_state, the covariance blocks and diagonal, init_feature, keep_features, keyframe reset, the generic update,
+ * the streaming kernels, the diagnostics) unpacks and mirrors first, in stream order; the form of every ring slot and of the
+ * batch's own buffers is tracked on the host and travels with snapshot / restore / select.  No entry point hands out a
+ * pointer to P itself. */
 typedef enum viekf_tuning {
   VIEKF_TUNE_RES_INSTANCE = 1, VIEKF_TUNE_UNIT_LAMBDA = 2, VIEKF_TUNE_BLOCK_GROUP = 3, VIEKF_TUNE_STREAM_MFMA = 4, VIEKF_TUNE_TILES = 5,
-  VIEKF_TUNE_PANEL_SERVICE = 6
+  VIEKF_TUNE_PANEL_SERVICE = 6, VIEKF_TUNE_PACKED_P = 7
 } viekf_tuning;
 int viekf_batch_set_tuning(viekf_batch *b, int32_t key, int32_t value);
 /* which kernels a feature-update step of this batch launches, as text (for logs and benchmark records; no reference

@@ -36,10 +36,20 @@ struct viekf_batch {
   //   0  all of P valid
   //   2  stale above the diagonal (left by the fused kernels, the matrix-core propagate and the grouped update: all of them read
   //      and write the lower triangle only)
-  // ensure_full_P mirrors the lower triangle up before anything that reads all of P.
+  //   3  the live P may be PACKED: not the column-major matrix but the fused kernel's own register and LDS image (ResPack,
+  //      viekf_instance_rows.hpp), left by a fused launch for the next one -- whole-batch mode only, never under per-filter
+  //      live slots or a participation mask (the batch would end up mixed)
+  // ensure_full_P(b, tolerate) brings the live P down to a level the caller can read: 3 -> 2 by unpacking (the fused kernel's
+  // own conversion launch), 2 -> 0 by mirroring the lower triangle up.  Levels are set through set_level only.
   int upper_stale = 0;
-  int stale_ever = 0;         // the highest level any launch of this batch has left: a ring slot is taken to be that stale when
-                              // it becomes (part of) the live state again -- slots carry no level of their own
+  int stale_ever = 0;         // the highest CANONICAL level (<= 2) any launch of this batch has left: a canonical ring slot is taken
+                              // to be that stale when it becomes (part of) the live state again
+  // Form of every buffer that can hold a whole batch's P: packed (1) or canonical (0) -- the batch's own buffers and each ring
+  // slot.  Set by whoever writes the buffer (a fused launch through P_out, ring copies, snapshot / restore), consulted when it
+  // becomes live.  Launches are uniform over the batch, so this is host state; the live buffer's entry is (upper_stale == 3).
+  unsigned char home_packed = 0;
+  std::vector<unsigned char> slot_packed;   // [hist_depth]
+  int tune_packed_p = 1;      // VIEKF_TUNE_PACKED_P: 0 = fused launches store canonical
   int hist_depth = 0;
   int live_slot = -1;        // >= 0: the live (x, P) ARE this slot of the history ring (d_x / d_P point into it)
   double *home_x = nullptr, *home_P = nullptr;   // the batch's own buffers (live state while live_slot < 0)
@@ -114,9 +124,28 @@ size_t hist_nP(const viekf_batch* b) { return sizeof(double) * (size_t)b->B * b-
 double* slot_x(const viekf_batch* b, int slot) { return reinterpret_cast<double*>(reinterpret_cast<char*>(b->h_x) + hist_nx(b) * slot); }
 double* slot_P(const viekf_batch* b, int slot) { return reinterpret_cast<double*>(reinterpret_cast<char*>(b->h_P) + hist_nP(b) * slot); }
 
-// A covariance is copied into and out of the ring as it stands, stale upper triangle included, and slots carry no level of
-// their own: what becomes (part of) the live state again is taken to be as stale as anything this batch ever produced.
-void mark_restored_stale(viekf_batch* b) { b->upper_stale = std::max(b->stale_ever, b->upper_stale); }
+// The packed / canonical entry of the buffer that holds the live P: a ring slot's or the batch's own buffers'.  Whole-batch mode
+// only: under per-filter live slots no single buffer is live, every buffer stays canonical and there is no entry (nullptr).
+unsigned char* live_form(viekf_batch* b) {
+  if (b->per_filter) return nullptr;
+  return b->live_slot >= 0 ? &b->slot_packed[(size_t)b->live_slot] : &b->home_packed;
+}
+// The one place the live level changes, in every mode: keeps the live buffer's form entry (where there is one) and stale_ever
+// with it.  Callers do not branch on per_filter.
+void set_level(viekf_batch* b, int level) {
+  b->upper_stale = level;
+  if (unsigned char* f = live_form(b)) *f = level == 3;
+  b->stale_ever = std::max(b->stale_ever, std::min(level, 2));
+}
+// A covariance is copied into and out of the ring as it stands, stale upper triangle included.  A buffer's FORM is known
+// (home_packed / slot_packed); a canonical buffer carries no level of its own: what becomes (part of) the live state again is
+// taken to be as stale as anything canonical this batch ever produced.
+void mark_restored_stale(viekf_batch* b) { b->upper_stale = std::min(2, std::max(b->stale_ever, b->upper_stale)); }
+// ... the live P now IS (a copy of) a whole-batch buffer of form `packed` (whole-batch mode: both callers refuse per-filter mode)
+void mark_live_from(viekf_batch* b, bool packed) {
+  if (packed) b->upper_stale = 3; else mark_restored_stale(b);
+  if (unsigned char* f = live_form(b)) *f = packed;
+}
 
 // lambda = 1 on the bearing components, or no partial update at all: the fused kernel's unit-Lambda (ZU) instances apply
 bool unit_lambda(const viekf_params& p) { return !p.use_partial_update || (p.lambda_feat[0] == 1.0 && p.lambda_feat[1] == 1.0); }

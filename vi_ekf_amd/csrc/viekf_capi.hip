@@ -109,10 +109,7 @@ int viekf_batch_create(int32_t batch, int32_t num_features, const viekf_params* 
   // of 5.2 TB/s with the wide-P pass's access pattern, the N = 150 step went from 5.66 to 5.3 ms.  The on-chip family reads and
   // writes P once per launch and is 0.9 % SLOWER with padded columns at N = 50 (0.3495 against 0.3464 ms, three alternating runs
   // of each on one box: 239 instead of 226 MB of P next to the 256 MiB Infinity Cache): it keeps the dense stride.
-  b->ld = num_features > 77 ? (b->n + 15) & ~15 : (b->n + 1) & ~1;
-#ifdef VIEKF_LD_PAD_ALL               // (diagnostic build, tools/build_variant.sh: A/B of the padded stride on the on-chip family)
-  b->ld = (b->n + 15) & ~15;
-#endif
+  b->ld = cov_ld(num_features);   // (N > 77: columns on whole lines; viekf_host.hpp)
   b->params = *p;
   DevParams& d = b->dp;
   std::memcpy(d.Qu, p->Qu, sizeof d.Qu);
@@ -204,7 +201,7 @@ int viekf_batch_reset(viekf_batch* b) {
   StreamArgs a = make_args(b);
   hipLaunchKernelGGL(k_reset, dim3(b->B), dim3(256), 0, b->stream, a, b->d_x0, b->d_Pdiag);
   HIP_TRY(hipGetLastError());
-  b->upper_stale = 0;
+  set_level(b, 0);   // (k_reset writes all of P)
   HIP_TRY(hipStreamSynchronize(b->stream));
   return VIEKF_OK;
 }
@@ -233,6 +230,9 @@ int viekf_batch_describe(const viekf_batch* b, char* out, int32_t cap) {
     snprintf(buf, sizeof buf, "k_step_resident<%d,%d>%s: %d worker waves x %d blocks + %d service wave%s, %s per CU (LDS %zu KB)",
              r.RB, r.NW, b->res_zu ? " ZU" : "", r.NW, r.RB, r.NS, r.NS > 1 ? "s" : "",
              r.max_lds_kb <= 40 ? "4 workgroups" : (r.max_lds_kb <= 80 ? "2 workgroups" : "1 workgroup"), b->res_lds / 1024);
+    const size_t len = strlen(buf);
+    snprintf(buf + len, sizeof buf - len, "; P %s between launches",
+             (b->tune_packed_p && packed_fits(b) && !b->per_filter) ? "packed" : "canonical");
   } else {
     const int bg = blocked_group(b, nullptr);
     if (bg > 0)
@@ -293,8 +293,13 @@ int viekf_batch_set_tuning(viekf_batch* b, int32_t key, int32_t value) {
   switch (key) {
     case VIEKF_TUNE_RES_INSTANCE:
       if (value < -1 || value >= kNumResInst) return fail(VIEKF_ERR_INVALID, "no such resident instance");
+      if (int rc = canonicalize_all(b)) return rc;   // (a packed image is defined by the instance's ownership map: gone below)
       b->tune_res_inst = value;
       break;
+    case VIEKF_TUNE_PACKED_P:
+      if (int rc = ensure_full_P(b, 2)) return rc;   // (ring slots keep their form: it is recorded per slot)
+      b->tune_packed_p = value != 0;
+      return VIEKF_OK;
     case VIEKF_TUNE_UNIT_LAMBDA:
       b->tune_unit_lambda = value != 0;
       b->res_zu = b->tune_unit_lambda && unit_lambda(b->params);
@@ -381,7 +386,7 @@ int viekf_batch_set_state(viekf_batch* b, const double* x, const double* P, cons
     const long tot = (long)b->n * b->n;
     hipLaunchKernelGGL(k_symmetrize, dim3((unsigned)((tot + 255) / 256), b->B), dim3(256), 0, b->stream, a);
     HIP_TRY(hipGetLastError());
-    b->upper_stale = 0;
+    set_level(b, 0);   // (all of P was given)
   }
   if (where == VIEKF_HOST) HIP_TRY(hipStreamSynchronize(b->stream));
   return VIEKF_OK;
@@ -417,6 +422,7 @@ int viekf_batch_init_feature(viekf_batch* b, const double* pix, const double* de
   if (int rc = check_batch(b)) return rc;
   if (!pix) return fail(VIEKF_ERR_INVALID, "pix must not be null");
   HIP_TRY(hipSetDevice(b->device));
+  if (int rc = need_canonical_P(b)) return rc;   // (writes the new feature's rows and columns in place)
   const double *d_pix = nullptr, *d_depth = nullptr;
   const uint8_t* d_mask = nullptr;
   int* d_ok = nullptr;
@@ -452,7 +458,7 @@ static int update_or_step(viekf_batch* b, const double* u, const double* dt, boo
     return rc;
   if (use_resident(b)) {
     if (with_propagate || M > 0)
-      if (int rc = launch_resident(b, with_propagate, d_u, d_dt, d_z, d_slot, M, d_R, r_mode, d_res, nullptr, nullptr, K)) return rc;
+      if (int rc = launch_resident(b, with_propagate, d_u, d_dt, d_z, d_slot, M, d_R, r_mode, d_res, -1, K)) return rc;
   } else {
     if (with_propagate)
       for (int k = 0; k < K; k++)
@@ -626,6 +632,7 @@ int viekf_batch_get_cov_diag(viekf_batch* b, double* diag, viekf_mem where) {
   if (int rc = check_batch(b)) return rc;
   if (!diag) return fail(VIEKF_ERR_INVALID, "diag is null");
   HIP_TRY(hipSetDevice(b->device));
+  if (int rc = need_canonical_P(b)) return rc;
   double* d_o = nullptr;
   Staged st(b, where);
   if (int rc = st.begin(out(diag, (size_t)b->B * b->n, &d_o))) return rc;
@@ -666,7 +673,9 @@ int viekf_batch_history_resize(viekf_batch* b, int32_t depth) {
     HIP_TRY(hipMemcpy(b->home_x, b->d_x, hist_nx(b), hipMemcpyDeviceToDevice));
     HIP_TRY(hipMemcpy(b->home_P, b->d_P, hist_nP(b), hipMemcpyDeviceToDevice));
     b->d_x = b->home_x; b->d_P = b->home_P; b->live_slot = -1;
+    b->home_packed = b->upper_stale == 3;   // (copied as it stands)
   }
+  b->slot_packed.clear();
   if (b->h_x) { HIP_TRY(hipFree(b->h_x)); b->h_x = nullptr; }
   if (b->h_P) { HIP_TRY(hipFree(b->h_P)); b->h_P = nullptr; }
   if (b->h_len) { HIP_TRY(hipFree(b->h_len)); b->h_len = nullptr; }
@@ -676,6 +685,7 @@ int viekf_batch_history_resize(viekf_batch* b, int32_t depth) {
   HIP_TRY(hipMalloc(&b->h_P, sizeof(double) * (size_t)depth * b->B * b->n * b->ld));
   HIP_TRY(hipMalloc(&b->h_len, sizeof(int) * (size_t)depth * b->B));
   b->hist_depth = depth;
+  b->slot_packed.assign((size_t)depth, 0);
   return VIEKF_OK;
 }
 
@@ -683,7 +693,8 @@ static int history_copy(viekf_batch* b, int32_t slot, bool save) {
   if (int rc = check_batch(b)) return rc;
   if (slot < 0 || slot >= b->hist_depth) return fail(VIEKF_ERR_INVALID, "snapshot slot out of range (viekf_batch_history_resize first)");
   if (b->per_filter) return fail(VIEKF_ERR_INVALID, "whole-batch ring copies under per-filter live slots (viekf_batch_select_filters)");
-  if (!save) mark_restored_stale(b);
+  // (the covariance is copied as it stands, packed or not: the form travels with it)
+  if (save) b->slot_packed[(size_t)slot] = b->upper_stale == 3; else mark_live_from(b, b->slot_packed[(size_t)slot] != 0);
   HIP_TRY(hipSetDevice(b->device));
   const size_t nl = sizeof(int) * (size_t)b->B;
   char* hl = reinterpret_cast<char*>(b->h_len) + nl * slot;
@@ -736,6 +747,7 @@ static int ring_filters(viekf_batch* b, const int32_t* slot, viekf_mem where, in
   if (where == VIEKF_HOST)
     for (int i = 0; i < b->B; i++)
       if (slot[i] >= b->hist_depth) return fail(VIEKF_ERR_INVALID, "ring slot out of range");
+  if (int rc = canonicalize_all(b)) return rc;   // (single filters move between buffers: no buffer may end up of mixed form)
   if (!to_ring) mark_restored_stale(b);
   const int* d_slot = nullptr;
   Staged st(b, where);
@@ -758,11 +770,11 @@ int viekf_batch_select(viekf_batch* b, int32_t slot) {
   if (int rc = check_batch(b)) return rc;
   if (slot < -1 || slot >= b->hist_depth) return fail(VIEKF_ERR_INVALID, "ring slot out of range (viekf_batch_history_resize first)");
   if (b->per_filter) return fail(VIEKF_ERR_INVALID, "viekf_batch_select under per-filter live slots (viekf_batch_select_filters)");
-  mark_restored_stale(b);
   if (!b->home_x) { b->home_x = b->d_x; b->home_P = b->d_P; }
   b->live_slot = slot;
   b->d_x = slot < 0 ? b->home_x : slot_x(b, slot);
   b->d_P = slot < 0 ? b->home_P : slot_P(b, slot);
+  mark_live_from(b, *live_form(b) != 0);   // (the buffer's own form; canonical: as stale as anything this batch produced)
   return VIEKF_OK;
 }
 
@@ -780,12 +792,13 @@ int viekf_batch_propagate_to(viekf_batch* b, const double* u, const double* dt, 
   Staged st(b, where);
   if (int rc = st.begin(in(u, (size_t)6 * b->B, &d_u), in(dt, (size_t)b->B, &d_dt))) return rc;
   if (use_resident(b)) {   // the fused kernel loads P from the live slot and stores it into the destination: no copy at all
-    if (int rc = launch_resident(b, true, d_u, d_dt, nullptr, nullptr, 0, nullptr, 0, nullptr, slot_x(b, dst_slot), slot_P(b, dst_slot)))
+    if (int rc = launch_resident(b, true, d_u, d_dt, nullptr, nullptr, 0, nullptr, 0, nullptr, dst_slot))
       return rc;
     if (int rc = viekf_batch_select(b, dst_slot)) return rc;
   } else {                 // streaming family works in place: copy, then propagate the copy
     HIP_TRY(hipMemcpyAsync(slot_x(b, dst_slot), b->d_x, hist_nx(b), hipMemcpyDeviceToDevice, b->stream));
     HIP_TRY(hipMemcpyAsync(slot_P(b, dst_slot), b->d_P, hist_nP(b), hipMemcpyDeviceToDevice, b->stream));
+    b->slot_packed[(size_t)dst_slot] = b->upper_stale == 3;
     if (int rc = viekf_batch_select(b, dst_slot)) return rc;
     if (int rc = launch_propagate(b, d_u, d_dt)) return rc;
   }
@@ -817,7 +830,7 @@ int viekf_batch_propagate_n_to(viekf_batch* b, int32_t K, const double* u, const
   const int last = dst_slots[K - 1];
   // ONE launch of the fused kernel: P is loaded from the live slot, stays on chip through the K propagates and is stored into the
   // last slot only
-  if (int rc = launch_resident(b, true, d_u, d_dt, nullptr, nullptr, 0, nullptr, 0, nullptr, slot_x(b, last), slot_P(b, last), K)) return rc;
+  if (int rc = launch_resident(b, true, d_u, d_dt, nullptr, nullptr, 0, nullptr, 0, nullptr, last, K)) return rc;
   if (int rc = viekf_batch_select(b, last)) return rc;
   if (intermediates_written) *intermediates_written = 0;
   return st.finish(true);
@@ -833,6 +846,7 @@ int viekf_batch_select_filters(viekf_batch* b, const int32_t* slot) {
     if (slot[i] < 0 && !b->per_filter) return fail(VIEKF_ERR_INVALID, "the first call has to name a slot for every filter");
   }
   HIP_TRY(hipSetDevice(b->device));
+  if (int rc = canonicalize_all(b)) return rc;   // (per-filter live slots keep today's canonical path: every buffer first)
   if (!b->per_filter) {
     if (!b->d_smap) HIP_TRY(hipMalloc(&b->d_smap, sizeof(int) * (size_t)b->B));
     if (!b->home_x) { b->home_x = b->d_x; b->home_P = b->d_P; }
@@ -890,7 +904,7 @@ int viekf_batch_propagate_filters_to(viekf_batch* b, const double* u, const doub
   b->active_on = true; b->d_active = const_cast<unsigned char*>(d_act);
   int rc = VIEKF_OK;
   if (!in_place) {           // the fused kernel loads filter b from its live slot and stores it into dst_slot[b]: no copy at all
-    rc = launch_resident(b, true, d_u, d_dt, nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, 1, d_omap);
+    rc = launch_resident(b, true, d_u, d_dt, nullptr, nullptr, 0, nullptr, 0, nullptr, -1, 1, d_omap);
     for (size_t i = 0; i < B && rc == VIEKF_OK; i++)     // (the kernel moves the device's map entries itself)
       if (dst_slot[i] >= 0) b->live_slots[i] = dst_slot[i];
   } else {                   // the HBM-path family works in place: copy slot -> slot, then propagate the copy
@@ -955,7 +969,7 @@ int viekf_batch_propagate_n_filters_to(viekf_batch* b, int32_t Kmax, const doubl
     const bool saved_on = b->active_on;
     unsigned char* saved_mask = b->d_active;
     b->active_on = true; b->d_active = const_cast<unsigned char*>(d_act);
-    const int rc = launch_resident(b, true, d_u, d_dt, nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, kmax, d_omap, d_kc);
+    const int rc = launch_resident(b, true, d_u, d_dt, nullptr, nullptr, 0, nullptr, 0, nullptr, -1, kmax, d_omap, d_kc);
     b->active_on = saved_on; b->d_active = saved_mask;
     if (rc) return rc;
     for (size_t i = 0; i < B; i++)   // (the launch is issued: the kernel moves the device's map entries itself)
@@ -1034,6 +1048,7 @@ int viekf_diag_consistency(viekf_batch* b, const double* x_true, double* logdet,
   if (!logdet && !nees && !whitened && !info) return fail(VIEKF_ERR_INVALID, "at least one output must not be null");
   if (!x_true && (nees || whitened)) return fail(VIEKF_ERR_INVALID, "nees and whitened need x_true");
   HIP_TRY(hipSetDevice(b->device));
+  if (int rc = need_canonical_P(b)) return rc;
   const size_t B = (size_t)b->B;
   const double* d_xt = nullptr;
   double *d_ld = nullptr, *d_ne = nullptr, *d_wh = nullptr;
@@ -1083,6 +1098,7 @@ int viekf_diag_innovation(viekf_batch* b, int32_t type, int32_t M, const double*
   if (needs_slot && !slot) return fail(VIEKF_ERR_INVALID, "slot must not be null for feature measurements");
   if (!needs_slot && (M != 1 || slot)) return fail(VIEKF_ERR_INVALID, "this measurement model takes M == 1 and no slot");
   HIP_TRY(hipSetDevice(b->device));
+  if (int rc = need_canonical_P(b)) return rc;
   const size_t BM = (size_t)b->B * (size_t)M, rr = (size_t)rdim * rdim;
   const double *d_z = nullptr, *d_R = nullptr;
   const int32_t* d_slot = nullptr;

@@ -52,22 +52,9 @@ size_t lds_propagate(const viekf_batch* b) {
 size_t lds_update(const viekf_batch* b) { return sizeof(double) * (size_t)(b->nxs + 5 * b->n + 32); }
 
 // A grouped update (k_update_feat_blocked) keeps only the lower triangle of P current; the matrix-core propagate reads only
-// that and rewrites all of P.  Everything else reads P whole: mirror the lower triangle up first.
-int ensure_full_P(viekf_batch* b, int tolerate = 0) {
-  if (b->upper_stale <= tolerate) return VIEKF_OK;
-  StreamArgs a = make_args(b);
-  const int nt = (b->n + 31) / 32;
-  hipLaunchKernelGGL(k_mirror_upper, dim3((unsigned)(nt * (nt + 1) / 2), b->B), dim3(256), 0, b->stream, a);
-  HIP_TRY(hipGetLastError());
-  b->upper_stale = 0;
-  return VIEKF_OK;
-}
-// ... for the entry points that read all of P, ahead of their argument checks
-int need_full_P(viekf_batch* b) {
-  if (!b->upper_stale) return VIEKF_OK;
-  HIP_TRY(hipSetDevice(b->device));
-  return ensure_full_P(b);
-}
+// that and rewrites all of P; a fused launch may leave P packed.  Everything else reads P whole (or at least canonical): see
+// ensure_full_P below the kernel tables.
+int ensure_full_P(viekf_batch* b, int tolerate = 0);
 
 // (VIEKF_TUNE_STREAM_MFMA = 0 keeps the kernels without matrix-core passes: experiments)
 bool stream_mfma_ok(const viekf_batch* b) { return b->tune_stream_mfma != 0; }
@@ -85,8 +72,7 @@ int launch_propagate(viekf_batch* b, const double* d_u, const double* d_dt) {
       hipLaunchKernelGGL((k_propagate_stream<512, true>), dim3(b->B), dim3(512), lds_propagate(b) + sizeof(double) * (9 * (size_t)b->N + 2),
                          b->stream, a, d_u, d_dt);
     }
-    b->upper_stale = 2;
-    b->stale_ever = 2;
+    set_level(b, 2);
   } else
     hipLaunchKernelGGL((k_propagate_stream<kThreads, false>), dim3(b->B), dim3(kThreads), lds_propagate(b), b->stream, a, d_u,
                        d_dt);
@@ -128,6 +114,7 @@ int blocked_group(const viekf_batch* b, size_t* lds_bytes) {
 
 int launch_update(viekf_batch* b, const double* d_z, const int* d_slot, int M, const double* d_R, int r_mode,
                   int* d_res) {
+  if (int rc = ensure_full_P(b, 2)) return rc;   // (a fused launch may have left P packed)
   StreamArgs a = make_args(b);
   long rsb = 0, rsm = 0;
   r_strides(r_mode, M, &rsb, &rsm);
@@ -142,8 +129,7 @@ int launch_update(viekf_batch* b, const double* d_z, const int* d_slot, int M, c
     static size_t have[64][6] = {};
     if (int rc = raise_dyn_lds({kern}, blds, have[b->device & 63][(bg == 32 ? 2 : (bg == 24 ? 1 : 0)) + (sv ? 3 : 0)])) return rc;
     hipLaunchKernelGGL(kern, dim3(b->B), dim3(512), blds, b->stream, a, d_z, d_slot, M, d_R, rsb, rsm, d_res);
-    b->upper_stale = 2;   // (reads and writes the lower triangle only)
-    b->stale_ever = 2;
+    set_level(b, 2);   // (reads and writes the lower triangle only)
   } else {
     if (int rc = ensure_full_P(b)) return rc;   // (the one-measurement kernel reads whole columns)
     hipLaunchKernelGGL(k_update_feat_stream<kThreads>, dim3(b->B), dim3(kThreads), lds_update(b), b->stream, a, d_z,
@@ -174,6 +160,70 @@ static_assert(sizeof(kTileKernels) / sizeof(kTileKernels[0]) == kNumTileInst, "o
 
 res_kernel_t res_kernel(int inst, bool multi, bool zu) { return kResKernels[inst].k[(multi ? 1 : 0) + (zu ? 2 : 0)]; }
 res_kernel_t tile_kernel(int inst, bool multi) { return kTileKernels[inst].k[multi ? 1 : 0]; }
+
+// May a fused launch of this batch's instance keep P packed?  THE fit rule (ResPack::fits, viekf_instance_rows.hpp).
+bool packed_fits(const viekf_batch* b) {
+  if (b->res_inst < 0) return false;
+  const ResInst& r = kResInst[b->res_inst];
+  return ResPack(b->N, r.RB, r.NW).fits(b->n, b->ld);
+}
+
+// Unpack: the packed image in (x, P) -- a whole batch's buffer, live or a ring slot -- becomes the canonical lower triangle, in
+// place.  A conversion-only launch of the fused kernel itself (no propagate, M = 0, packed load, canonical store,
+// RES_FMT_P_ONLY): every workgroup loads its whole image before its first store, the arithmetic between load and store is
+// skipped (nothing pending), x, status and result buffers are not written -- an identity on everything but P's form.
+int unpack_buffer(viekf_batch* b, double* x, double* P) {
+  StreamArgs a = make_args(b);
+  a.x = a.x_out = x; a.P = a.P_out = P;
+  a.smap = nullptr; a.smap_out = nullptr; a.active = nullptr;
+  const ResInst& r = kResInst[b->res_inst];
+  hipLaunchKernelGGL(res_kernel(b->res_inst, false, b->res_zu), dim3((unsigned)b->B), dim3((r.NW + r.NS) * 64), b->res_lds, b->stream, a,
+                     (RES_FMT_LOAD_PACKED | RES_FMT_P_ONLY) << 1, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, 0L, 0L, nullptr);
+  HIP_TRY(hipGetLastError());
+  return VIEKF_OK;
+}
+
+int ensure_full_P(viekf_batch* b, int tolerate) {
+  if (b->upper_stale <= tolerate) return VIEKF_OK;
+  if (b->upper_stale == 3) {   // stage one: packed -> lower triangle valid
+    if (int rc = unpack_buffer(b, b->d_x, b->d_P)) return rc;
+    set_level(b, 2);
+    if (tolerate >= 2) return VIEKF_OK;
+  }
+  StreamArgs a = make_args(b);   // stage two: mirror the lower triangle up
+  const int nt = (b->n + 31) / 32;
+  hipLaunchKernelGGL(k_mirror_upper, dim3((unsigned)(nt * (nt + 1) / 2), b->B), dim3(256), 0, b->stream, a);
+  HIP_TRY(hipGetLastError());
+  set_level(b, 0);
+  return VIEKF_OK;
+}
+// ... for the entry points that read all of P, ahead of their argument checks
+int need_full_P(viekf_batch* b) {
+  if (!b->upper_stale) return VIEKF_OK;
+  HIP_TRY(hipSetDevice(b->device));
+  return ensure_full_P(b);
+}
+// ... and for those that read or write elements of the lower triangle in place (init_feature, the diagnostics, the diagonal)
+int need_canonical_P(viekf_batch* b) {
+  if (b->upper_stale < 3) return VIEKF_OK;
+  HIP_TRY(hipSetDevice(b->device));
+  return ensure_full_P(b, 2);
+}
+// Every buffer of the batch canonical: before the ownership map changes (setup_resident) and before anything that moves single
+// filters between buffers (per-filter ring copies and live slots) -- a buffer must never hold filters of both forms.
+int canonicalize_all(viekf_batch* b) {
+  if (int rc = ensure_full_P(b, 2)) return rc;
+  for (int s = 0; s < (int)b->slot_packed.size(); s++)
+    if (b->slot_packed[(size_t)s]) {
+      if (int rc = unpack_buffer(b, slot_x(b, s), slot_P(b, s))) return rc;
+      b->slot_packed[(size_t)s] = 0;
+    }
+  if (b->home_packed && b->home_P) {
+    if (int rc = unpack_buffer(b, b->home_x, b->home_P)) return rc;
+  }
+  b->home_packed = 0;
+  return VIEKF_OK;
+}
 
 int setup_tiles(viekf_batch* b) {
   b->tile_inst = -1;
@@ -249,11 +299,20 @@ bool use_resident(const viekf_batch* b) { return (b->res_inst >= 0 || b->tile_in
 
 // one launch handles at most res_mcap(N) measurements; longer lists are chunked (P makes one extra HBM round trip per chunk)
 int launch_resident(viekf_batch* b, bool do_prop, const double* d_u, const double* d_dt, const double* d_z,
-                    const int* d_slot, int M, const double* d_R, int r_mode, int* d_res, double* x_out = nullptr,
-                    double* P_out = nullptr, int KP = 1, const int* smap_out = nullptr, const int* kcount = nullptr) {
+                    const int* d_slot, int M, const double* d_R, int r_mode, int* d_res, int dst_slot = -1, int KP = 1,
+                    const int* smap_out = nullptr, const int* kcount = nullptr) {
+  // dst_slot >= 0: the launch stores (x, P) into that slot of the history ring instead of in place (a single-chunk launch:
+  // viekf_batch_propagate_to / _propagate_n_to); the caller makes the slot live afterwards (viekf_batch_select)
   // (the fused kernel loads the lower triangle only and stores the lower triangle only: no symmetrisation before or after)
+  // Form of P: the resident family keeps P PACKED from one launch to the next -- nobody reads the canonical matrix in between --
+  // where the image fits, the batch advances as a whole (no per-filter live slots, no participation mask: the buffer would end up
+  // mixed) and VIEKF_TUNE_PACKED_P is on.  The load form is whatever the live P is; everything else gets canonical P first.
+  const bool store_packed = !use_tiles(b) && !b->per_filter && !b->active_on && b->tune_packed_p != 0 && packed_fits(b);
+  if (use_tiles(b) || b->per_filter || b->active_on)
+    if (int rc = ensure_full_P(b, 2)) return rc;
+  int fmt = (b->upper_stale == 3 ? RES_FMT_LOAD_PACKED : 0) | (store_packed ? RES_FMT_STORE_PACKED : 0);
   StreamArgs a = make_args(b);
-  if (x_out) { a.x_out = x_out; a.P_out = P_out; }   // (only meaningful for a single-chunk launch)
+  if (dst_slot >= 0) { a.x_out = slot_x(b, dst_slot); a.P_out = slot_P(b, dst_slot); }
   a.smap_out = smap_out;
   a.kcount = kcount;   // (per-filter propagate counts: the resident multi-propagate instances, KP > 1, read them; KP is their maximum)
   long rsb = 0, rsm = 0;
@@ -269,14 +328,21 @@ int launch_resident(viekf_batch* b, bool do_prop, const double* d_u, const doubl
     const int cap = res_mcap(b->N);
     const int mc = (M - m0 < cap) ? (M - m0) : cap;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, b->stream, a,
-                       ((do_prop && m0 == 0) ? (1 | (KP << 16)) : 0) | ((dbg_bits() & 0xff) << 8), d_u, d_dt, d_z ? d_z + 2L * m0 : nullptr,
+                       ((do_prop && m0 == 0) ? (1 | (KP << 16)) : 0) | (fmt << 1) | ((dbg_bits() & 0xff) << 8), d_u, d_dt, d_z ? d_z + 2L * m0 : nullptr,
                        d_slot ? d_slot + m0 : nullptr, mc, M, d_R ? d_R + rsm * m0 : nullptr, rsb, rsm,
                        d_res ? d_res + m0 : nullptr);
     HIP_TRY(hipGetLastError());
     m0 += mc;
+    // (a further chunk loads what this one stored -- which is NOT the form this one loaded when the live P was packed and this
+    //  launch stores canonical: a restored packed slot with the switch off, say)
+    fmt = (fmt & ~RES_FMT_LOAD_PACKED) | (store_packed ? RES_FMT_LOAD_PACKED : 0);
   } while (m0 < M);
-  b->upper_stale = 2;
-  b->stale_ever = 2;
+  if (dst_slot >= 0) {   // another ring slot was written: its form is recorded, the caller makes it live
+    b->slot_packed[(size_t)dst_slot] = store_packed;
+    b->stale_ever = 2;
+  } else {
+    set_level(b, store_packed ? 3 : 2);
+  }
   return VIEKF_OK;
 }
 

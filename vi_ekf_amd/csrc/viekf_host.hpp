@@ -15,4 +15,13 @@ int set_last_error(int code, const std::string& msg);
 // block ownership map [RB][64 * NWV] of the fused-step kernel (viekf_resmap.cpp); false when the blocks do not fit
 bool build_resmap(int N, int RB, int NWV, std::vector<int>& map, int* used_slots = nullptr);
 
+// Column stride of P for num_features features (viekf_batch_create explains the choice)
+inline int cov_ld(int num_features) {
+  const int n = 16 + 3 * num_features;
+#ifdef VIEKF_LD_PAD_ALL               // (diagnostic build, tools/build_variant.sh: A/B of the padded stride on the on-chip family)
+  return (n + 15) & ~15;
+#endif
+  return num_features > 77 ? (n + 15) & ~15 : (n + 1) & ~1;
+}
+
 }  // namespace viekf

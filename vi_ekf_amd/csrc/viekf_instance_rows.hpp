@@ -46,6 +46,23 @@ namespace viekf {
 struct ResInst { int RB, NW, NS, nmin, nmax, max_lds_kb; };
 struct TileInst { int NT, NW, max_lds_kb, pair; };
 
+// The PACKED image of P: between two fused launches a filter's n * ld doubles of the P buffer may hold the
+// kernel's own register and LDS image instead of the column-major matrix -- offsets in doubles from the filter's P:
+//   [0, single)       the worker threads' blocks: register q = 9 * slot + element of thread t, in pairs (q, q + 1) of 16
+//                     bytes per lane, pair p of the TW = 64 NW threads contiguous: offset 2 (p TW + t) + (q & 1)
+//   [single, pbc)     the last register of an odd count (9 RB odd), 8 bytes per lane: offset single + t
+//   [pbc, pbb)        the body columns as they sit in LDS, Pbc[3N][16];   [pbb, total)  the body block Pbb[16][16]
+// The map (thread, slot) -> block is build_resmap's, so an image is defined by (instance row, N).  THE FIT RULE: the packed
+// form is used only where `total` <= n * ld (fits); a small N on a wide instance does not fit and stays canonical.
+struct ResPack {
+  int TW, npair, single, pbc, pbb, total;
+  constexpr ResPack(int N, int RB, int NW)
+      : TW(64 * NW), npair(9 * RB / 2), single(2 * (9 * RB / 2) * 64 * NW), pbc(single + ((9 * RB) & 1) * 64 * NW),
+        pbb(pbc + 48 * N), total(pbc + 48 * N + 256) {}
+  constexpr int elem(int q, int t) const { return q < 2 * npair ? 2 * ((q >> 1) * TW + t) + (q & 1) : single + t; }
+  constexpr bool fits(int n, int ld) const { return (long)total <= (long)n * ld; }
+};
+
 #define VIEKF_RES_ROW(RB, NW, NS, NMIN, NMAX, KB) {RB, NW, NS, NMIN, NMAX, KB},
 #define VIEKF_TILE_ROWS(NT, NW, PAIR_KB, SINGLE_KB) {NT, NW, PAIR_KB, 1}, {NT, NW, SINGLE_KB, 0},
 inline constexpr ResInst kResInst[] = {VIEKF_RES_LIST(VIEKF_RES_ROW)};

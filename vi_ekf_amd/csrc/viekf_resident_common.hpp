@@ -3,9 +3,16 @@
 #pragma once
 #include <type_traits>
 
+#include "viekf_instance_rows.hpp"
 #include "viekf_kernels_stream.hpp"
 
 namespace viekf {
+
+// Format bits of a fused launch (bits 1..3 of the launch word, uniform over the launch, set by launch_resident): which form of
+// P the launch loads and which it stores -- canonical column-major P[n][ld] (lower triangle valid) or the packed image of the
+// kernel's own registers and LDS (ResPack, viekf_instance_rows.hpp) -- and the conversion-only launch (no propagate, M = 0):
+// it leaves x, the status words and the result buffers alone, so packed -> canonical is an identity on everything but the form.
+constexpr int RES_FMT_LOAD_PACKED = 1, RES_FMT_STORE_PACKED = 2, RES_FMT_P_ONLY = 4;
 
 #ifndef RES_INLINE
 #define RES_INLINE __forceinline__
@@ -145,6 +152,7 @@ struct ResShared {  // resolved LDS pointers + launch constants shared by both r
   int2* mseq;   // [res_mcap(N)] {index of the next measurement that runs (or M), its slot (or -1)}: one LDS read per iteration
   BodyCtx* ctx;
   int N, n, nf, len, M, mstride, do_prop, b, dbg, kp, B, img_len, mcap;   // kp: propagates per launch (viekf_batch_step_n)
+  int fmt;      // RES_FMT_* bits of this launch
   long si, so;   // the filter's entry of x / P it is loaded from and stored to (StreamArgs::si / so, read ONCE in the prologue)
   double* stamps;
 };

@@ -457,15 +457,17 @@ __device__ __forceinline__ void res_service(const StreamArgs& a, const ResShared
   // ---------------- store x, status ----------------
   double* xg = a.x_out + S.so * a.nxs;
   const int xend = (a.x_out != a.x || a.smap_out) ? a.nxs : xZ + 5 * len;   // another ring slot gets the whole vector (zeros past the features)
-  for (int i = lane; PRIMARY && i < xend; i += 64) {
+  const bool p_only = (S.fmt & RES_FMT_P_ONLY) != 0;   // a conversion of P's form: x and the status word stay untouched
+  for (int i = lane; PRIMARY && !p_only && i < xend; i += 64) {
     const double v = xs[i];
     if (v != v) flag |= FLAG_NAN;
     if (v > 1e6) flag |= FLAG_BLOWUP;
     xg[i] = v;
   }
-  if (flag) atomicOr(&a.flags[S.b], flag);
+  if (flag && !p_only) atomicOr(&a.flags[S.b], flag);
   RES_STAMP(S, lane == 0, 13);
-  {   // cooperative store of P (see res_store_chunk): this wave streams its share of every chunk
+  if (!(S.fmt & RES_FMT_STORE_PACKED)) {   // cooperative store of P (see res_store_chunk): this wave streams its share of every chunk
+                                           // (the packed store is the workers' alone: no chunk image, no barrier)
     StoreChunk sc;
     for (int f0 = 0; store_chunk_at(f0, N, n, S.img_len, sc); f0 = sc.f1) {
       __syncthreads();   // S1

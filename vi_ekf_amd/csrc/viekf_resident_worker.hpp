@@ -57,6 +57,28 @@ __device__ __forceinline__ void res_store_chunk(const StreamArgs& a, const ResSh
   }
 }
 
+// The packed form of P (ResPack, viekf_instance_rows.hpp): the worker threads' registers and the LDS-resident body part as they
+// stand, 16 bytes per lane and 1 KB contiguous per wave instruction -- no ownership conversion, no barrier.  A lane that owns no
+// block in a slot stores and reloads whatever it holds there: blk() says "not owned" for it, so it is never published or stored
+// canonically.  img = the filter's P (16-byte aligned: n * ld is even); t = worker thread.
+template <int RB, int TW>
+__device__ __forceinline__ void res_store_packed(double* img, const double (&pb)[RB][9], const double* Pbc, const double* Pbb,
+                                                 int N, int t) {
+  constexpr ResPack K(0, RB, TW / 64);
+  v2f64* dst = reinterpret_cast<v2f64*>(img) + t;
+#pragma unroll
+  for (int p = 0; p < K.npair; p++) {
+    v2f64 v;
+    v.x = pb[(2 * p) / 9][(2 * p) % 9];
+    v.y = pb[(2 * p + 1) / 9][(2 * p + 1) % 9];
+    dst[p * TW] = v;
+  }
+  if ((9 * RB) & 1) img[K.single + t] = pb[RB - 1][8];
+  v2f64* gc = reinterpret_cast<v2f64*>(img + K.pbc);
+  for (int e = t; e < 24 * N; e += TW) gc[e] = *reinterpret_cast<const v2f64*>(Pbc + 2 * e);
+  v2f64* gb = reinterpret_cast<v2f64*>(img + K.pbc + 48 * N);
+  for (int e = t; e < 128; e += TW) gb[e] = *reinterpret_cast<const v2f64*>(Pbb + 2 * e);
+}
 // Body columns of an update, in LDS: item = (feature g, k pair j) = the 3 rows of one feature x 2 body columns (6 elements),
 // items [first, last) strided over `nthreads` callers; the mask Lambda of a (feature row, body column) pair comes from the
 // table Lbc [3][16] (prologue).  The owner of the item of the feature measured two phases from now also adds its rows -- as
@@ -126,6 +148,20 @@ __device__ __forceinline__ void res_worker(const StreamArgs& a, const ResShared&
   const bool own_diag = tid_ < N;   // slot 0 of this thread is the diagonal block (I, I), I = tid
 
   double pb[RB][9];   // pb[a][r*3+s] = P[16+3I+r][16+3J+s]
+  // Load format (uniform over the launch): canonical -- the gather below -- or the image a packed store of this instance left
+  // (res_store_packed).  The blocks take ONE instruction stream for both: each register's offset from the filter's P is selected,
+  // not its value -- a branch with two bodies merges 63 register pairs per thread and cost this kernel 10 VGPRs and a spill in
+  // the propagate (7 blocks per thread), the select costs none in the update loop.  Packed, a wave's 8-byte loads cover 1 KB
+  // contiguous, the two halves of a pair from the same lines.
+  const bool ldp = (S.fmt & RES_FMT_LOAD_PACKED) != 0;
+  if (ldp) {   // the LDS-resident part, as it sat in LDS: 16 bytes per lane
+    const int t = opaque(tid_);
+    constexpr ResPack K(0, RB, TW / 64);
+    const v2f64* gc = reinterpret_cast<const v2f64*>(P + K.pbc);
+    for (int e = t; e < 24 * N; e += TW) *reinterpret_cast<v2f64*>(Pbc + 2 * e) = gc[e];
+    const v2f64* gb = reinterpret_cast<const v2f64*>(P + K.pbc + 48 * N);
+    for (int e = t; e < 128; e += TW) *reinterpret_cast<v2f64*>(Pbb + 2 * e) = gb[e];
+  }
   {
     const int tq = opaque(tid_);
 #pragma unroll
@@ -136,23 +172,28 @@ __device__ __forceinline__ void res_worker(const StreamArgs& a, const ResShared&
       // of its mirror, a diagonal block takes its lower triangle for both
       const bool up = I < J;
       const int br = 16 + 3 * (up ? J : I), bc = 16 + 3 * (up ? I : J);
-      const double* pu = P + (br + (long)bc * ld);
+      // (offsets in doubles from P, 32 bits: < n * ld.  Packed: lane part 2 t of a 16-byte pair -- t of the odd last register)
+      const unsigned cbase = (unsigned)(br + bc * ld);
+      const unsigned base = ldp ? 2u * (unsigned)tq : cbase, base1 = ldp ? (unsigned)tq : cbase;
 #pragma unroll
       for (int s = 0; s < 3; s++)
 #pragma unroll
         for (int r = 0; r < 3; r++) {
           const int rr = (I == J) ? max(r, s) : (up ? s : r), cc = (I == J) ? min(r, s) : (up ? r : s);
-          pb[ia][r * 3 + s] = pu[rr + (long)cc * ld];
+          constexpr ResPack K(0, RB, TW / 64);
+          const int q = ia * 9 + r * 3 + s;
+          const unsigned offp = (unsigned)K.elem(q, 0), offc = (unsigned)(rr + cc * ld);
+          pb[ia][r * 3 + s] = P[((q < 2 * K.npair) ? base : base1) + (ldp ? offp : offc)];
         }
     }
     // body columns -> LDS (coalesced along rows)
-    for (int e = tid; e < nf * 16; e += TW) {
+    for (int e = tid; !ldp && e < nf * 16; e += TW) {
       const int k = e / nf, row = e - k * nf;
       Pbc[row * 16 + k] = P[(16 + row) + (long)k * ld];
     }
     // (the body block is kept EXACTLY symmetric, like every other part of P here -- see sym_diag below: both copies of a pair
     //  are loaded from the lower triangle)
-    for (int e = tid; e < 256; e += TW) {
+    for (int e = tid; !ldp && e < 256; e += TW) {
       const int r = e & 15, c = e >> 4;
       Pbb[r * 16 + c] = P[max(r, c) + (long)min(r, c) * ld];
     }
@@ -492,8 +533,10 @@ __device__ __forceinline__ void res_worker(const StreamArgs& a, const ResShared&
 
   // ---------------- store ----------------
   // (indices re-derived from opaque copies: otherwise the load addresses are kept alive -- spilled -- all kernel long)
-  {
-    P = a.P_out + S.so * n * ld;   // in place, or the next slot of the history ring
+  P = a.P_out + S.so * n * ld;   // in place, or the next slot of the history ring
+  if (S.fmt & RES_FMT_STORE_PACKED) {   // (uniform over the launch: the service wave skips the chunk barriers likewise)
+    res_store_packed<RB, TW>(P, pb, Pbc, Pbb, N, opaque(tid_));
+  } else {
     for (int e = opaque(tid); e < nf * 16; e += TW) {     // body columns, coalesced along rows
       const int k = e / nf, row = e - k * nf;
       P[(16 + row) + (long)k * ld] = Pbc[row * 16 + k];

@@ -203,4 +203,18 @@ int viekf_debug_res_instance(int i, int* rb, int* nw, int* nmin, int* nmax) {
   return 0;
 }
 
+// diagnostic hook (not part of include/viekf.h; host arithmetic only): the packed image of P (ResPack, viekf_instance_rows.hpp)
+// of n_feat features on an instance with `rb` slots and `nw` worker waves.  elem[(9 * slot + element) * 64 nw + t] = offset, in
+// doubles from the filter's P, of that register of worker thread t; info[0..4] = {offset of Pbc [3 n_feat][16], offset of Pbb
+// [256], total, n * ld of the filter's P, fits (the host's rule)}.  tests/test_packed_layout_cpu.py checks its invariants.
+int viekf_debug_packed_layout(int n_feat, int rb, int nw, int32_t* elem, int32_t* info) {
+  if (n_feat < 1 || rb < 1 || nw < 1 || !elem || !info) return -1;
+  const viekf::ResPack K(n_feat, rb, nw);
+  for (int q = 0; q < 9 * rb; q++)
+    for (int t = 0; t < K.TW; t++) elem[(size_t)q * K.TW + t] = K.elem(q, t);
+  const int n = 16 + 3 * n_feat, ld = viekf::cov_ld(n_feat);
+  info[0] = K.pbc; info[1] = K.pbb; info[2] = K.total; info[3] = n * ld; info[4] = K.fits(n, ld) ? 1 : 0;
+  return 0;
+}
+
 }  // extern "C"
