@@ -259,7 +259,7 @@ int setup_resident(viekf_batch* b) {
     if (force && b->tune_res_inst != i) continue;
     if (b->N < r.nmin || b->N > r.nmax) continue;
     if (b->N * (b->N + 1) / 2 > r.RB * r.NW * 64 || b->N > r.NW * 64) continue;
-    const ResLds L(b->N, b->n, b->nxs);
+    const ResLds L(b->N, b->n, b->nxs, res_batched_loads(r.RB, r.NW));
     const size_t lds = sizeof(double) * (size_t)L.total;
     if (lds > (size_t)r.max_lds_kb * 1024) continue;
     if (r.max_lds_kb <= 80 && !force) {   // two small workgroups per CU only pay when the batch fills the CUs more than once

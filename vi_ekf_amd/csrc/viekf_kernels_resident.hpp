@@ -29,14 +29,14 @@ namespace viekf {
 // MP (the multi-propagate instances): the trip count of the propagate loop, S.kp, is this filter's own where the launch carries
 // per-filter counts (StreamArgs::kcount); it is one value for the whole workgroup, read here ONCE -- the service wave and the
 // worker waves both loop to S.kp and meet at the same barriers.
-template <int T, bool MP>
+template <int T, bool MP, bool BL>
 __device__ __forceinline__ void res_prologue(const StreamArgs& a, ResShared& S, double* smem, int do_prop,
                                              const double* __restrict__ dt_all, const double* __restrict__ z_all,
                                              const int* __restrict__ slot_all, int M, int m_stride,
                                              const double* __restrict__ R_all, long r_stride_b, long r_stride_m,
                                              int* __restrict__ result_all) {
   const int b = blockIdx.x, tid = threadIdx.x;
-  const ResLds L(a.N, a.n, a.nxs);
+  const ResLds L(a.N, a.n, a.nxs, BL);
   S.xs = smem + L.xs; S.Kt = smem + L.Kt; S.Wt = smem + L.Wt; S.Praw = smem + L.Praw; S.lam = smem + L.lam;
   S.sm = smem + L.sm; S.fixadd = smem + L.fixadd; S.fixset = smem + L.fixset; S.Z = smem + L.Z; S.img_len = L.img_len;
   S.phiff = smem + L.phiff; S.Abb = smem + L.Abb; S.Gb = smem + L.Gb; S.Phibb = smem + L.Phibb; S.Mbb = smem + L.Mbb;
@@ -57,6 +57,8 @@ __device__ __forceinline__ void res_prologue(const StreamArgs& a, ResShared& S, 
       const double lk = a.lambda[tid & 15], lq = a.lambda[16 + (tid >> 4)];
       S.Lbc[tid] = a.dp->use_partial_update ? (lk + lq - lq * lk) : 1.0;
     }
+    // launch constants of the propagate's barrier intervals (res_prop_setup, res_prop_body): read from LDS there, not from memory
+    if (BL && tid >= T - 22) { const int i = tid - (T - 22); S.sm[RES_SM_SQRTQU + i] = (i < 6) ? a.dp->sqrtQu[i] : a.Qx[i - 6]; }
     if (tid == 0) { S.sm[42] = (do_prop & 1) ? dt_all[b] : 0.0; S.sm[40] = 0.0; S.sm[41] = 0.0; S.sm[44] = 0.0; S.sm[45] = 0.0; S.sm[46] = 0.0; S.sm[49] = 0.0; S.sm[50] = 0.0; S.sm[51] = 0.0; S.sm[32] = 0.0; S.sm[33] = 0.0; S.sm[52] = 0.0; S.sm[53] = 0.0; S.sm[54] = 0.0; S.sm[36] = 0.0; S.sm[37] = 0.0; }
     for (int mm_ = tid; mm_ < M; mm_ += T) {
       const int slot = slot_all[(long)b * m_stride + mm_];
@@ -112,20 +114,21 @@ __global__ __launch_bounds__((NW + NS) * 64, (NW <= 3) ? 2 : 1) void k_step_resi
     }
   }
 #endif
+  constexpr bool BL = res_batched_loads(RB, NW);
   ResShared S;
-  res_prologue<T, MP>(a, S, smem, do_prop, dt_all, z_all, slot_all, M, m_stride, R_all, r_stride_b, r_stride_m, result_all);
+  res_prologue<T, MP, BL>(a, S, smem, do_prop, dt_all, z_all, slot_all, M, m_stride, R_all, r_stride_b, r_stride_m, result_all);
   // The service wave's chain is the floor of an update, so it should not share its SIMD's issue slots with a worker wave.  A
   // workgroup's waves go to the four SIMDs round-robin: with 7 waves (NW = 6, one service wave) the 4th one is alone on its
   // SIMD -- that is the service wave.  Otherwise the last wave(s) serve.
   constexpr int SVC = (NW == 6 && NS == 1) ? 3 : NW;
   const int wave = tid >> 6;
   if (NS == 2) {
-    if (wave == NW) res_service<T, MP, 1>(a, S, tid & 63, NW, u_all, dt_all, result_all);
-    else if (wave == NW + 1) res_service<T, MP, 2>(a, S, tid & 63, NW, u_all, dt_all, result_all);
-    else res_worker<RB, TW, MP, T, ZU>(a, S, tid);
+    if (wave == NW) res_service<T, MP, 1, BL>(a, S, tid & 63, NW, u_all, dt_all, result_all);
+    else if (wave == NW + 1) res_service<T, MP, 2, BL>(a, S, tid & 63, NW, u_all, dt_all, result_all);
+    else res_worker<RB, TW, MP, T, ZU, BL>(a, S, tid);
   } else {
-    if (wave == SVC) res_service<T, MP>(a, S, tid & 63, NW, u_all, dt_all, result_all);
-    else res_worker<RB, TW, MP, T, ZU>(a, S, tid - (wave > SVC ? 64 : 0));
+    if (wave == SVC) res_service<T, MP, 0, BL>(a, S, tid & 63, NW, u_all, dt_all, result_all);
+    else res_worker<RB, TW, MP, T, ZU, BL>(a, S, tid - (wave > SVC ? 64 : 0));
   }
 }
 

@@ -29,20 +29,25 @@ constexpr int ZK = 9;    // rank of the feature/body coupling
 constexpr int ZS = 26;   // row stride of Z: 6 ZS = 28 (mod 64 dwords), consecutive features land on distinct 16-byte bank groups
 
 // measurements per launch (the host chunks longer lists: P then makes one more HBM round trip per chunk): a frame that measures
-// every feature once fits one launch.  (64 up to 64 features: the headline instance is within 740 bytes of its 80 KB.)
+// every feature once fits one launch.  (64 up to 64 features: the headline instance, <7, 3> at N = 50, takes 81 488 of its
+// 81 920 bytes of LDS -- 432 are left.)
 __host__ __device__ inline int res_mcap(int N) { return N > 64 ? 80 : 64; }
+
+constexpr int RES_SM_SQRTQU = 64, RES_SM_QXB = 70;   // see ResLds::sm (resident family only: the tile family's sm has 64 words)
 
 struct ResLds {  // LDS carve-up in doubles, shared by host (size) and device (offsets)
   int xs, Kt, Wt, Praw, lam, sm, fixadd, fixset, Z, phiff, Abb, Gb, Phibb, Mbb, Gdb, Pbb, T16, xdb, ctx, Pbc, PhibbT, Pd, PsiP, Pi, Xi, AvG, Lbc, mslot, mseq, mz, mR, img_len, total;
-  __host__ __device__ ResLds(int N, int n, int nxs) {
+  __host__ __device__ ResLds(int N, int n, int nxs, bool staged) {   // staged: res_batched_loads of the instance
     const int nf = 3 * N;
     int o = 0;
     auto take = [&](int cnt) { int r = o; o += (cnt + 1) & ~1; return r; };
     xs = take(nxs);
     lam = take(n);
-    sm = take(64);   // [0..15],[16..31] two measurement mailboxes {Hb(4) res(2) Sinv(4) verdict}, [40..41] fix mailboxes
+    sm = take(staged ? 64 + 22 : 64);   // [0..15],[16..31] two measurement mailboxes {Hb(4) res(2) Sinv(4) verdict}, [40..41] fix mailboxes
                      // non-empty, [42] dt, [44..46] NaN-guard words (phase mod 3), [49] count of worker waves that have
-                     // published the next raw columns (int), [50..51] gate verdicts (phase parity)
+                     // published the next raw columns (int), [50..51] gate verdicts (phase parity), [64..69] sqrt(Qu) and
+                     // [70..85] Qx of the body rows: launch constants the propagate reads inside its barrier intervals
+                     // (RES_SM_SQRTQU, RES_SM_QXB: at fixed offsets from sm, they cost no pointer of their own; only where staged)
     fixadd = take(2 * (N > 0 ? N : 1)); fixset = take(2 * (N > 0 ? N : 1));
     // Z, Phi_ff and the two-lives region are contiguous: at store time all of it is dead and holds the P image
     Z = take(nf * ZS > 4 * n ? nf * ZS : 4 * n);   // propagate: the records; updates: second gain-row buffer; store: P image
@@ -156,6 +161,26 @@ struct ResShared {  // resolved LDS pointers + launch constants shared by both r
   long si, so;   // the filter's entry of x / P it is loaded from and stored to (StreamArgs::si / so, read ONCE in the prologue)
   double* stamps;
 };
+
+// Ownership words of worker thread t (build_resmap, viekf_resmap.cpp: entry [slot][t] = I | J << 8 | owned << 16).  A use site
+// loads ALL of its thread's words in one batch and decodes them in registers: a load per block, each waited for before the block's
+// own loads or LDS reads may issue, is one exposed memory round trip per block (7 in a row at 7 blocks per thread).
+template <int RB, int TW>
+__device__ __forceinline__ void res_words(const int* __restrict__ resmap, int t, int (&w)[RB]) {
+#pragma unroll
+  for (int ia = 0; ia < RB; ia++) w[ia] = resmap[ia * TW + t];
+}
+// Which instances do so, and stage sqrt(Qu) / Qx in LDS: all but the one-workgroup-per-CU instances <1,7>, <2,7>, <3,7> -- 1 to 3
+// blocks per thread leave next to nothing to batch, and their unit-Lambda step measured 0.7 - 1.4 % SLOWER with the batches -- and
+// <8,6> at the register file's end (its propagate-only launch +1.8 %, more spilled dwords).  Those compile to the instruction
+// stream they had before (profiles/serial_loads/).
+constexpr bool res_batched_loads(int RB, int NW) { return NW != 7 && RB != 8; }
+// false = not owned (then I = J = 0: every LDS / global read stays in range, results are never stored)
+__device__ __forceinline__ bool res_word_blk(int e, int& I, int& J) {
+  I = e & 0xff;
+  J = (e >> 8) & 0xff;
+  return (e >> 16) != 0;
+}
 
 // first m' >= from whose update will actually run (mslot >= 0), else M
 __device__ __forceinline__ int res_next_valid(const ResShared& S, int from) {

@@ -11,7 +11,7 @@ namespace viekf {
 // (N <= 114 by lanes; the register file ends the family at N = 72), features 64.. on its lanes 14...  A measurement is
 // predicted by the wave that holds its feature; the other one receives {Hb, residual, S^-1, gate} through an LDS mailbox
 // (polled; bounded); each wave writes the gain rows, the NaN-guard word and the fix_depth mailbox flag of its own rows.
-template <int T, bool MP, int ROLE = 0>
+template <int T, bool MP, int ROLE = 0, bool BL = true>
 __device__ __forceinline__ void res_service(const StreamArgs& a, const ResShared& S, int lane, int nww,
                                             const double* __restrict__ u_all, const double* __restrict__ dt_all,
                                             int* __restrict__ result_all) {
@@ -89,7 +89,7 @@ __device__ __forceinline__ void res_service(const StreamArgs& a, const ResShared
     }
     // One propagate per launch: this wave takes the body strips and the body block of P+ (res_prop_body: they need V, D, Xi,
     // ready since B3p, and write what no contraction reads) off the workers' path instead of waiting for them.
-    if (PRIMARY && !MP) res_prop_body<64>(a, S, lane);
+    if (PRIMARY && !MP) res_prop_body<64, BL>(a, S, lane);
     __syncthreads();  // B4p (workers finish the contraction and publish the new body columns / block)
     RES_STAMP(S, lane == 0, 8);
     if (PRIMARY && MP && kp + 1 < nkp) {

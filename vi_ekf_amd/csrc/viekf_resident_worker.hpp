@@ -59,7 +59,7 @@ __device__ __forceinline__ void res_store_chunk(const StreamArgs& a, const ResSh
 
 // The packed form of P (ResPack, viekf_instance_rows.hpp): the worker threads' registers and the LDS-resident body part as they
 // stand, 16 bytes per lane and 1 KB contiguous per wave instruction -- no ownership conversion, no barrier.  A lane that owns no
-// block in a slot stores and reloads whatever it holds there: blk() says "not owned" for it, so it is never published or stored
+// block in a slot stores and reloads whatever it holds there: its ownership word says "not owned", so it is never published or stored
 // canonically.  img = the filter's P (16-byte aligned: n * ld is even); t = worker thread.
 template <int RB, int TW>
 __device__ __forceinline__ void res_store_packed(double* img, const double (&pb)[RB][9], const double* Pbc, const double* Pbb,
@@ -124,7 +124,8 @@ __device__ __forceinline__ void res_body_items(const ResShared& S, const double*
 }
 // (The service wave takes no share of the body-column items: with the tile map its chain is the longest wave of an update and
 //  every share > 0 measured slower -- N = 50, B = 1024: 0 / N / 2 N items -> 0.348 / 0.347 / 0.353 ms per step.)
-template <int RB, int TW, bool MP, int T = TW + 64, bool ZU = false>
+// BL: the instance issues its launch-constant loads in batches (res_batched_loads, viekf_resident_common.hpp)
+template <int RB, int TW, bool MP, int T = TW + 64, bool ZU = false, bool BL = true>
 __device__ __forceinline__ void res_worker(const StreamArgs& a, const ResShared& S, int tid) {
   const int N = S.N, n = S.n, ld = a.ld, nf = S.nf, len = S.len;
   double* P = a.P + S.si * n * ld;
@@ -139,11 +140,12 @@ __device__ __forceinline__ void res_worker(const StreamArgs& a, const ResShared&
   double* Pbb = S.Pbb;   // [16][16]  row-major P_bb
   // (P[body rows, feature cols] is NOT kept: P is symmetric up to rounding, the mirror is written at store time)
   const int* __restrict__ resmap = a.resmap;
-  auto blk = [&](int t, int ia, int& I, int& J) -> bool {   // block ia of thread t; false = not owned (then I = J = 0: every
-    const int e = resmap[ia * TW + t];                       // LDS / global read stays in range, results are never stored)
-    I = e & 0xff;
-    J = (e >> 8) & 0xff;
-    return (e >> 16) != 0;
+  // (the ownership words are launch constants in memory: with BL every use site below loads its thread's RB words in ONE batch
+  //  -- res_words -- ahead of a barrier or of its own loads where it can, and decodes them in registers.  They are not kept across
+  //  the update loop: their addresses and values would be live -- spilled -- all kernel long.  Without BL a word is loaded where
+  //  its block is handled, as before.)
+  auto blk = [&](const int (&w)[RB], int t, int ia, int& I, int& J) -> bool {   // block ia of thread t; false = not owned
+    return res_word_blk(BL ? w[ia] : resmap[ia * TW + t], I, J);
   };
   const bool own_diag = tid_ < N;   // slot 0 of this thread is the diagonal block (I, I), I = tid
 
@@ -164,10 +166,12 @@ __device__ __forceinline__ void res_worker(const StreamArgs& a, const ResShared&
   }
   {
     const int tq = opaque(tid_);
+    int ew[RB];   // all words first: the 9 RB loads of P are then in flight together, behind counted waits on the words
+    if (BL) res_words<RB, TW>(resmap, tq, ew);
 #pragma unroll
     for (int ia = 0; ia < RB; ia++) {
       int I, J;
-      blk(tq, ia, I, J);
+      blk(ew, tq, ia, I, J);
       // only the lower triangle of P is valid in memory (see the store): a block above the diagonal is read as the transpose
       // of its mirror, a diagonal block takes its lower triangle for both
       const bool up = I < J;
@@ -231,13 +235,31 @@ __device__ __forceinline__ void res_worker(const StreamArgs& a, const ResShared&
   // (MP = false -- one propagate, every launch but viekf_batch_step_n's -- is a separate instance: the loop costs the
   //  single-propagate kernel 2 % in registers kept alive across it)
   const int nkp = MP ? S.kp : 1;
+  int eu[RB];
   if (S.do_prop)
    for (int kp = 0; kp < nkp; kp++) {
     // (the thread index is laundered per propagate: otherwise everything derived from it is hoisted out of this loop and
     //  kept alive across it -- spills)
     const int tk = MP ? opaque(tid) : tid;
     const double* Z = S.Z; double* phiff = S.phiff;
-    res_prop_setup<TW>(a, S, tk);
+    // the words of the local transforms and of the contraction, and Qx of this thread's diagonal block (slot 0 of the threads
+    // t < N: block (t, t)), are issued here: their round trip falls into the set-up, not behind the barrier
+    // (Qx is laid out per feature, so the triple is indexed by the thread's feature; the parameter set has ONE Qx_feat triple
+    //  for all features -- viekf_capi.hip fills every feature's three words with it -- so no test through the API can tell a
+    //  wrong feature index here from a right one: keep 16 + 3 t + r in step with build_resmap's slot 0 = block (t, t).  The
+    //  clamp only keeps the load of a thread without a diagonal block inside the array.)
+    int ep[RB];
+    double qd[3];
+    if (BL) {
+      const int tq = opaque(tid_);
+      res_words<RB, TW>(resmap, tq, ep);
+#pragma unroll
+      for (int r = 0; r < 3; r++) qd[r] = a.Qx[16 + 3 * min(tq, N - 1) + r];
+    }
+    // (multi-propagate instances: sqrt(Qu) stays a memory operand of the set-up -- cached after the first propagate; the LDS
+    //  operand cost them 16 .. 22 scalar-register reloads per update in the service loop)
+    if (MP || !BL) res_prop_setup<TW>(a, S, tk);
+    else res_prop_setup<TW, true>(a, S, tk);
     RES_STAMP(S, tid == 0, 66);
     __syncthreads();  // B3p
     RES_STAMP(S, tid == 0, 67);
@@ -246,9 +268,9 @@ __device__ __forceinline__ void res_worker(const StreamArgs& a, const ResShared&
     //      first each row times Phi_ff[J]^T, then each column times Phi_ff[I]  (keeps the register peak low)
 #pragma unroll
     for (int ia = 0; ia < RB; ia++) {
-      const int tq = opaque(tid_);
+      const int tq = BL ? 0 : opaque(tid_);
       int I, J;
-      const bool v = blk(tq, ia, I, J);
+      const bool v = blk(ep, tq, ia, I, J);
       const double* fj = phiff + 9 * J;
 #pragma unroll
       for (int r = 0; r < 3; r++) {
@@ -263,7 +285,9 @@ __device__ __forceinline__ void res_worker(const StreamArgs& a, const ResShared&
 #pragma unroll
         for (int r = 0; r < 3; r++) pb[ia][r * 3 + s] = fi[r * 3 + 0] * p0 + fi[r * 3 + 1] * p1 + fi[r * 3 + 2] * p2;
       }
-      if (v && I == J) {
+      if (BL) {
+        if (ia == 0 && own_diag) { pb[0][0] += qd[0]; pb[0][4] += qd[1]; pb[0][8] += qd[2]; }   // (the only diagonal blocks)
+      } else if (v && I == J) {
         pb[ia][0] += a.Qx[16 + 3 * I + 0];
         pb[ia][4] += a.Qx[16 + 3 * I + 1];
         pb[ia][8] += a.Qx[16 + 3 * I + 2];
@@ -283,11 +307,11 @@ __device__ __forceinline__ void res_worker(const StreamArgs& a, const ResShared&
     //  loop -- re-deriving them from the thread index cost as many instructions per k as the arithmetic)
     int zoff[RB];
     {
-      const int tq = opaque(tid_);
+      const int tq = BL ? 0 : opaque(tid_);
 #pragma unroll
       for (int ia = 0; ia < RB; ia++) {
         int I, J;
-        blk(tq, ia, I, J);
+        blk(ep, tq, ia, I, J);
         zoff[ia] = (3 * I * ZS) | ((3 * J * ZS) << 16);
       }
     }
@@ -320,7 +344,10 @@ __device__ __forceinline__ void res_worker(const StreamArgs& a, const ResShared&
     for (int k = ZK; k < ZK + 3; k++) contract(k, std::false_type{});
     sym_diag();
     RES_STAMP(S, tid == 0, 69);
-    if (MP) res_prop_body<TW>(a, S, tk);   // (single propagate: the service wave does this meanwhile, it would only wait)
+    // the words of the update loop's block indices: their round trip falls into the barrier wait (single propagate; the
+    // multi-propagate instances load them behind their last propagate, one round trip in K propagates)
+    if (BL && !MP) res_words<RB, TW>(resmap, opaque(tid_), eu);
+    if (MP) res_prop_body<TW, BL>(a, S, tk);   // (single propagate: the service wave does this meanwhile, it would only wait)
     par ^= 1;   // the service wave posted propagate's fix_depth edits into mailbox 0
     RES_STAMP(S, tid == 0, 70);
     __syncthreads();  // B4p
@@ -336,8 +363,9 @@ __device__ __forceinline__ void res_worker(const StreamArgs& a, const ResShared&
   // block indices of this thread, computed once (symmetric ownership left enough registers to keep them)
   int Ib[RB], Jb[RB];
   bool vb[RB];
+  if (BL && (MP || !S.do_prop)) res_words<RB, TW>(resmap, opaque(tid_), eu);
 #pragma unroll
-  for (int ia = 0; ia < RB; ia++) vb[ia] = blk(tid_, ia, Ib[ia], Jb[ia]);
+  for (int ia = 0; ia < RB; ia++) vb[ia] = blk(eu, tid_, ia, Ib[ia], Jb[ia]);
   const double p0rr = uniform_f64(prm.P0_feat[2]);   // (read here: a global load inside the update loop would put vmcnt waits there)
   // Lambda of the body block's two elements of this thread's task (one task per thread where 128 threads share the 128 tasks):
   // constants of the launch, not re-formed from three LDS words in every update
@@ -537,6 +565,8 @@ __device__ __forceinline__ void res_worker(const StreamArgs& a, const ResShared&
   if (S.fmt & RES_FMT_STORE_PACKED) {   // (uniform over the launch: the service wave skips the chunk barriers likewise)
     res_store_packed<RB, TW>(P, pb, Pbc, Pbb, N, opaque(tid_));
   } else {
+    int es[RB];   // (one batch for all chunks, issued ahead of the body-column pass)
+    if (BL) res_words<RB, TW>(resmap, opaque(tid_), es);
     for (int e = opaque(tid); e < nf * 16; e += TW) {     // body columns, coalesced along rows
       const int k = e / nf, row = e - k * nf;
       P[(16 + row) + (long)k * ld] = Pbc[row * 16 + k];
@@ -549,11 +579,11 @@ __device__ __forceinline__ void res_worker(const StreamArgs& a, const ResShared&
     int ch = 0;
     for (int f0 = 0; store_chunk_at(f0, N, n, S.img_len, sc); f0 = sc.f1, ch++) {
       const int f1 = sc.f1;
-      const int tq = opaque(tid_);
+      const int tq = BL ? 0 : opaque(tid_);
 #pragma unroll
       for (int ia = 0; ia < RB; ia++) {
         int I, J;
-        if (blk(tq, ia, I, J)) {
+        if (blk(es, tq, ia, I, J)) {
           // the block in its lower-triangle orientation: (I, J) itself for I >= J, its mirror (J, I) otherwise
           if (I >= J && J >= f0 && J < f1) {                // rows of feature I in the columns of feature J
             double* d = img + (3 * (J - f0)) * sc.h + (16 + 3 * I - sc.rb);
