@@ -234,6 +234,89 @@ def test_fix_depth_inside_the_updates(N, kernel):
     assert_close(g.get_covariance(), np.stack([f.P for f in fs]), "P")
 
 
+_RESET_SCENES = {}   # N -> the scene and the oracle's outcome of test_fix_depth_reset_branch_inside_the_updates (computed once per N)
+
+
+def _reset_scene(N, x, P):
+    """The scene of test_fix_depth_inside_the_updates with every other even feature just below rho = 1e2, and the oracle's N
+    updates applied one by one, counting the fix_depth resets each one causes.  x, P: state and covariance of a fresh batch."""
+    if N not in _RESET_SCENES:
+        B = x.shape[0]
+        sc = scene.make_scene(B, N, 1, seed=77 + N)
+        x0, P0, x, P = x, P, x.copy(), P.copy()
+        for f in range(0, N, 2):
+            d = 16 + 3 * f
+            x[:, 17 + 5 * f + 4] = 2e-3 if f % 4 == 0 else 100.0 - 2e-3
+            P[:, d + 2, d + 2] = 4.0
+            P[:, d + 2, d] = P[:, d, d + 2] = 0.1
+            P[:, d + 2, d + 1] = P[:, d + 1, d + 2] = -0.1
+        z = sc["z"][0] + np.random.default_rng(5).normal(0.0, 1.5, sc["z"][0].shape)
+        reset, p0rr = 1.0 / (2.0 * sc["params"]["min_depth"]), sc["params"]["P0_feat"][2]
+        irho, idiag = 17 + 5 * np.arange(N) + 4, 16 + 3 * np.arange(N) + 2
+        fs, codes, big, neg = [], np.zeros(sc["slot"].shape, dtype=np.int32), 0, 0
+        for b in range(B):
+            f = orc.OracleFilter(N).init(**oracle_params(sc["params"]))
+            for i in range(N):
+                f.init_feature(sc["pix"][b, i], i)
+            f.x[:] = x[b]
+            f.P[:] = P[b]
+            for m in range(sc["slot"].shape[1]):
+                before = f.x[irho].copy()
+                codes[b, m] = f.update(orc.FEAT, z[b, m], sc["R"], True, int(sc["slot"][b, m]))
+                fixed = (f.x[irho] == reset) & (before != reset)          # fix_depth put rho back (vi_ekf_helper.cpp:128-156) ...
+                at_p0 = f.P[idiag, idiag] == p0rr                         # ... and set P(rho,rho) (rho > 1e2) or added to it (rho < 0)
+                big += int((fixed & at_p0).sum())
+                neg += int((fixed & ~at_p0).sum())
+            fs.append(f)
+        x_ref, P_ref = np.stack([f.x for f in fs]), np.stack([f.P for f in fs])
+        print("N = %d: %d resets on rho > 1e2, %d on rho < 0, %d gated" % (N, big, neg, int((codes == 1).sum())))
+        # the oracle alone: the scene takes both branches, gates nothing and stays finite
+        assert big >= 1, "no update pushed a feature past rho = 1e2: the test does not test what it says"
+        assert neg >= 1, "no update pushed a feature below rho = 0"
+        assert (codes == 0).all(), codes
+        assert np.isfinite(x_ref).all() and np.isfinite(P_ref).all()
+        for a in (x, P, z, x_ref, P_ref, codes):
+            a.setflags(write=False)
+        _RESET_SCENES[N] = dict(sc=sc, x0=x0, P0=P0, x=x, P=P, z=z, x_ref=x_ref, P_ref=P_ref, codes=codes)
+    return _RESET_SCENES[N]
+
+
+# (N, kernel of make_gpu, a tuning or None, what describe() names)
+RESET_ROUTES = [(6, 1, None, "k_update_feat_panelsvc"),                            # the look-ahead grouped update
+                (6, 1, ("TUNE_STREAM_MFMA", 0), "k_update_feat_stream"),           # the reference-order kernel
+                (90, 0, None, "k_update_feat_panelsvc"),                           # wide P, automatic choice
+                (90, 0, ("TUNE_PANEL_SERVICE", 0), "k_update_feat_blocked"),
+                (6, 2, None, "k_step_resident"), (24, 2, None, "k_step_resident"),
+                (50, 0, ("TUNE_RES_INSTANCE", 6), "k_step_resident<7,3>"),         # the 256-thread headline instance: the loop without MERGE
+                (56, 2, None, "k_step_resident"), (68, 2, None, "k_step_resident"),   # two service waves
+                (50, 3, None, "k_step_tiles<"), (50, 5, None, "k_step_tiles_pair")]
+
+
+@pytest.mark.parametrize("N,kernel,tune,name", RESET_ROUTES,
+                         ids=["%d-k%d%s" % (r[0], r[1], "-%s=%d" % r[2] if r[2] else "") for r in RESET_ROUTES])
+def test_fix_depth_reset_branch_inside_the_updates(N, kernel, tune, name):
+    """The rho > 1e2 branch of fix_depth (reset of rho, P(rho,rho) = P0_feat[2]; vi_ekf_helper.cpp:151-154) after an UPDATE
+    (vi_ekf_meas.cpp:271), on every route of the feature update.  The scene of test_fix_depth_inside_the_updates, with every
+    other even feature starting at rho = 100 - 2e-3, and update_feat alone: a propagate in front would move those features far
+    from the threshold through the feature dynamics.  The noisy pixels push some of them past 1e2 and others below 0."""
+    from vi_ekf_amd import capi
+    B = 12
+    g = make_gpu(scene.make_scene(B, N, 1, seed=77 + N), B, N, kernel=kernel)
+    if tune:
+        g.set_tuning(getattr(capi, tune[0]), tune[1])
+    assert name in g.describe(), g.describe()
+    x0, P0 = g.get_state(), g.get_covariance()
+    ref = _reset_scene(N, x0, P0)
+    assert np.array_equal(x0, ref["x0"]) and np.array_equal(P0, ref["P0"])   # (every route starts where the shared reference did)
+    sc = ref["sc"]
+    g.set_state(x=ref["x"].copy(), P=ref["P"].copy())
+    res = g.update_feat(ref["z"].copy(), sc["slot"], sc["R"])
+    assert (res == ref["codes"]).all(), (res, ref["codes"])
+    assert_close(g.get_state(), ref["x_ref"], "x")
+    assert_close(g.get_covariance(), ref["P_ref"], "P")
+    assert ((g.get_status() & 4) != 0).any()
+
+
 @pytest.mark.parametrize("N", [3, 10])
 def test_fix_depth_branches(N):
     """force rho < 0 and rho > 1e2 (reference vi_ekf_helper.cpp:128-156): a rare branch needs its own test"""

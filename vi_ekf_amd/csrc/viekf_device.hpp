@@ -322,6 +322,28 @@ VD void inv2(const double* S, double* Si) {
   Si[0] = x00; Si[1] = x10; Si[2] = x01; Si[3] = x11;
 }
 
+// Innovation gate (vi_ekf_meas.cpp:234-239): a measurement whose Mahalanobis distance exceeds this is rejected
+constexpr double kGateMahal = 9.0;
+
+constexpr unsigned FLAG_NAN = 1u, FLAG_BLOWUP = 2u, FLAG_NEGDEPTH = 4u, FLAG_INTERNAL = 8u;
+
+// fix_depth (vi_ekf_helper.cpp:128-156), the rule: repairs the inverse depth `rho` in place (reset = 1 / (2 min_depth)), raises
+// the status bits and says what is due on P(rho,rho): nothing,  += err^2  (p_add(err^2)), or  = P0_feat[2]  (p_set()).  Every
+// kernel family applies that edit to its own storage of the diagonal: memory, a register, the fused step's fix mailbox.
+template <class PAdd, class PSet>
+VD void fix_depth_rule(double& rho, double reset, unsigned& flag, PAdd&& p_add, PSet&& p_set) {
+  if (rho != rho) { rho = reset; flag |= FLAG_NAN; }
+  if (rho < 0.0) {
+    const double err = reset - rho;
+    p_add(err * err);
+    rho = reset;
+    flag |= FLAG_NEGDEPTH;
+  } else if (rho > 1e2) {
+    p_set();
+    rho = reset;
+  }
+}
+
 // init_feature's state part (vi_ekf_feat.cpp:13-36): pixel -> bearing quaternion, inverse depth
 VD void init_feature_state(const double* pix, double depth, const DevParams& p, double* q, double* rho) {
   const double l0 = pix[0] - p.cam_center[0], l1 = pix[1] - p.cam_center[1];

@@ -120,6 +120,34 @@ __device__ __forceinline__ void inv2_fast(const double* S, double* Si) {
   Si[0] = S[3] * r; Si[1] = -S[1] * r; Si[2] = -S[2] * r; Si[3] = S[0] * r;
 }
 
+// Innovation of a pixel measurement (vi_ekf_meas.cpp:230-234) from the 2x2 block of H and the feature's P_zeta,zeta:
+//   S = Hb P_zz Hb^T + R  (R column-major),  Si = S^-1;  returns the Mahalanobis distance  r^T S^-1 r  for the gate.
+__device__ __forceinline__ double feat_innovation(const double* Hb, double p00, double p01, double p10, double p11, const double* R,
+                                                  double r0, double r1, double* Si) {
+  const double w00 = p00 * Hb[0] + p01 * Hb[1], w01 = p00 * Hb[2] + p01 * Hb[3];   // (P_zz Hb^T)
+  const double w10 = p10 * Hb[0] + p11 * Hb[1], w11 = p10 * Hb[2] + p11 * Hb[3];
+  double S[4];
+  S[0] = Hb[0] * w00 + Hb[1] * w10 + R[0];
+  S[1] = Hb[0] * w01 + Hb[1] * w11 + R[2];
+  S[2] = Hb[2] * w00 + Hb[3] * w10 + R[1];
+  S[3] = Hb[2] * w01 + Hb[3] * w11 + R[3];
+  inv2_fast(S, Si);
+  return (r0 * Si[0] + r1 * Si[2]) * r0 + (r0 * Si[1] + r1 * Si[3]) * r1;
+}
+
+// qn <- exp(v) (x) qn  (sgn = 1: a bearing quaternion)  or  qn (x) exp(v)  (sgn = -1: the attitude); the two products share
+// every term but the sign of the cross product (src/quat.cpp:304-312), so one instruction stream serves lanes of both kinds
+__device__ __forceinline__ void q_step_signed(const double* v, double sgn, double* qn) {
+  double e[4];
+  q_exp_fast(v, e);
+  const double ex = sgn * e[1], ey = sgn * e[2], ez = sgn * e[3];
+  const double o0 = e[0] * qn[0] - e[1] * qn[1] - e[2] * qn[2] - e[3] * qn[3];
+  const double o1 = e[0] * qn[1] + qn[0] * e[1] + (ey * qn[3] - ez * qn[2]);
+  const double o2 = e[0] * qn[2] + qn[0] * e[2] + (ez * qn[1] - ex * qn[3]);
+  const double o3 = e[0] * qn[3] + qn[0] * e[3] + (ex * qn[2] - ey * qn[1]);
+  qn[0] = o0; qn[1] = o1; qn[2] = o2; qn[3] = o3;
+}
+
 __device__ __forceinline__ void q_feat_boxplus_fast(const double* q, double d0, double d1, double* o) {
   double t1[3], t2[3], z[3], v[3], e[4];
   bearing_frame_fast(q, t1, t2, z);

@@ -172,25 +172,20 @@ __global__ __launch_bounds__(T) void k_diag_consistency(StreamArgs a, int b0, co
       }
     }
   }
-  // e = x_true [-] x as row m (the arithmetic of k_boxops, reference vi_ekf_helper.cpp:100-111)
+  // e = x_true [-] x as row m (vi_ekf_helper.cpp:100-111, as k_boxops)
   if (x_true) {
     const double* x1 = x_true + (long)b * a.nx;
     if (tid == 0) {
-      double o[16], d3[3];
-      for (int i = 0; i < 6; i++) o[dxPOS + i] = x1[xPOS + i] - x2[xPOS + i];
-      q_boxminus_dev(x1 + xATT, x2 + xATT, d3);
-      for (int i = 0; i < 3; i++) o[dxATT + i] = d3[i];
-      for (int i = 0; i < 7; i++) o[dxB_A + i] = x1[xB_A + i] - x2[xB_A + i];
+      double o[16];
+      body_boxminus_dev(x1, x2, o);
       for (int j = 0; j < 16; j++) A[cs(j) + (m - j)] = o[j];
     }
     for (int f = tid - 64; f < len; f += T)
       if (f >= 0) {
-        double d2[2];
-        q_feat_boxminus_dev(x1 + xZ + 5 * f, x2 + xZ + 5 * f, d2);
+        double d[3];
+        feat_boxminus_dev(x1 + xZ + 5 * f, x2 + xZ + 5 * f, d);
         const int j = dxZ + 3 * f;
-        A[cs(j) + (m - j)] = d2[0];
-        A[cs(j + 1) + (m - j - 1)] = d2[1];
-        A[cs(j + 2) + (m - j - 2)] = x1[xZ + 5 * f + 4] - x2[xZ + 5 * f + 4];
+        for (int k = 0; k < 3; k++) A[cs(j + k) + (m - j - k)] = d[k];
       }
   } else {
     for (int j = tid; j < m; j += T) A[cs(j) + (m - j)] = 0.0;
@@ -234,7 +229,7 @@ __global__ __launch_bounds__(64) void k_diag_innovation(StreamArgs a, int type, 
   const int b = (int)(e / M), mi = (int)(e - (long)b * M);
   const double nan = __longlong_as_double(0x7ff8000000000000LL);
   const int len = min(max(a.len[b], 0), a.N);
-  const bool needs_slot = type == MT_QZETA || type == MT_FEAT || type == MT_DEPTH || type == MT_INV_DEPTH;
+  const bool needs_slot = meas_needs_slot(type);
   const int slot = (needs_slot && slot_all) ? slot_all[e] : 0;
   double r3[3] = {nan, nan, nan}, S[9], mahal = nan;
   for (int i = 0; i < 9; i++) S[i] = nan;
@@ -247,9 +242,7 @@ __global__ __launch_bounds__(64) void k_diag_innovation(StreamArgs a, int type, 
     double Hc[18], zhat[4] = {0.0, 0.0, 0.0, 0.0}, W[6][3], Sr[9], Si[9];
     meas_model(type, xs, slot, *a.dp, zhat, cols, Hc, nc);
     r3[0] = r3[1] = r3[2] = 0.0;
-    if (type == MT_QZETA) q_feat_boxminus_dev(z, zhat, r3);            // :210-213
-    else if (type == MT_ATT) q_boxminus_dev(z, zhat, r3);              // :214-217
-    else for (int i = 0; i < zdim && i < 3; i++) r3[i] = z[i] - zhat[i];
+    meas_residual(type, z, zhat, zdim, r3);
     for (int ci = 0; ci < nc; ci++) {                                  // W = P H^T at the rows H touches
       double w[3] = {0.0, 0.0, 0.0};
       for (int c = 0; c < nc; c++) {

@@ -109,19 +109,8 @@ __global__ __launch_bounds__(64) void k_boxops(StreamArgs a, int minus, const do
     const double* x2 = v_all + (long)b * nx;
     double* o = out_all + (long)b * n;
     for (int i = dxZ + 3 * len + tid; i < n; i += 64) o[i] = 0.0;
-    if (tid == 0) {                                                       // :102-104
-      for (int i = 0; i < 6; i++) o[dxPOS + i] = x1[xPOS + i] - x2[xPOS + i];
-      double d3[3];
-      q_boxminus_dev(x1 + xATT, x2 + xATT, d3);
-      for (int i = 0; i < 3; i++) o[dxATT + i] = d3[i];
-      for (int i = 0; i < 7; i++) o[dxB_A + i] = x1[xB_A + i] - x2[xB_A + i];
-    }
-    for (int f = tid; f < len; f += 64) {                                 // :106-110
-      double d2[2];
-      q_feat_boxminus_dev(x1 + xZ + 5 * f, x2 + xZ + 5 * f, d2);
-      o[dxZ + 3 * f] = d2[0]; o[dxZ + 3 * f + 1] = d2[1];
-      o[dxZ + 3 * f + 2] = x1[xZ + 5 * f + 4] - x2[xZ + 5 * f + 4];
-    }
+    if (tid == 0) body_boxminus_dev(x1, x2, o);                           // :102-104
+    for (int f = tid; f < len; f += 64) feat_boxminus_dev(x1 + xZ + 5 * f, x2 + xZ + 5 * f, o + dxZ + 3 * f);   // :106-110
   }
 }
 

@@ -64,23 +64,12 @@ struct WsLayout {
   }
 };
 
-constexpr unsigned FLAG_NAN = 1u, FLAG_BLOWUP = 2u, FLAG_NEGDEPTH = 4u, FLAG_INTERNAL = 8u;
-
 // fix_depth (vi_ekf_helper.cpp:128-156) for feature i of the block's filter; xs is the LDS copy of x
 __device__ __forceinline__ void fix_depth_one(double* xs, double* P, int ld, int i, const DevParams& p, unsigned& flag) {
   const int xR = xZ + 5 * i + 4, dR = dxZ + 3 * i + 2;
   double rho = xs[xR];
-  const double reset = 1.0 / (2.0 * p.min_depth);
-  if (rho != rho) { rho = reset; flag |= FLAG_NAN; }
-  if (rho < 0.0) {
-    const double err = reset - rho;
-    P[dR + (long)dR * ld] += err * err;
-    rho = reset;
-    flag |= FLAG_NEGDEPTH;
-  } else if (rho > 1e2) {
-    P[dR + (long)dR * ld] = p.P0_feat[2];
-    rho = reset;
-  }
+  fix_depth_rule(rho, 1.0 / (2.0 * p.min_depth), flag, [&](double e2) { P[dR + (long)dR * ld] += e2; },
+                 [&] { P[dR + (long)dR * ld] = p.P0_feat[2]; });
   xs[xR] = rho;
 }
 
@@ -438,6 +427,8 @@ __global__ __launch_bounds__(T) void k_propagate_stream(StreamArgs a, const doub
 
 // ------------------------------------------------------------------------------------------------
 // M sequential active FEAT updates: VIEKF::update + h_feat (vi_ekf_meas.cpp:196-278, 354-367)
+// The reference-order baseline the tests compare the other update kernels with: it deliberately keeps h_feat, the LU inv2 and
+// W from LDS written out here instead of the fast forms (h_feat_frame, feat_innovation) the other families share.
 // ------------------------------------------------------------------------------------------------
 template <int T>
 __global__ __launch_bounds__(T) void k_update_feat_stream(StreamArgs a, const double* __restrict__ z_all,
@@ -502,7 +493,7 @@ __global__ __launch_bounds__(T) void k_update_feat_stream(StreamArgs a, const do
     inv2(S, Si);
     const double r0 = sm[6], r1 = sm[7];
     const double mahal = (r0 * Si[0] + r1 * Si[2]) * r0 + (r0 * Si[1] + r1 * Si[3]) * r1;  // vi_ekf_meas.cpp:234
-    if (mahal > 9.0) {                                   // gate (:235-239): returns before fix_depth
+    if (mahal > kGateMahal) {                                   // gate (:235-239): returns before fix_depth
       if (res && tid == 0) *res = 1;
       __syncthreads();
       continue;
@@ -828,17 +819,7 @@ __global__ __launch_bounds__(T) void k_update_feat_blocked(StreamArgs a, const d
       for (int f = tid; f < len; f += T) {
         const int xR = xZ + 5 * f + 4;
         double rho = xs[xR];
-        const double reset = 1.0 / (2.0 * prm.min_depth);
-        if (rho != rho) { rho = reset; flag |= FLAG_NAN; }
-        if (rho < 0.0) {
-          const double err = reset - rho;
-          diag[f] += err * err;
-          rho = reset;
-          flag |= FLAG_NEGDEPTH;
-        } else if (rho > 1e2) {
-          diag[f] = prm.P0_feat[2];
-          rho = reset;
-        }
+        fix_depth_rule(rho, 1.0 / (2.0 * prm.min_depth), flag, [&](double e2) { diag[f] += e2; }, [&] { diag[f] = prm.P0_feat[2]; });
         xs[xR] = rho;
       }
     };
@@ -858,20 +839,10 @@ __global__ __launch_bounds__(T) void k_update_feat_blocked(StreamArgs a, const d
       }
       const double h00 = Hb[0], h01 = Hb[1], h10 = Hb[2], h11 = Hb[3];
       const double r0 = wz[2 * wi] - zhat[0], r1 = wz[2 * wi + 1] - zhat[1];   // residual (vi_ekf_meas.cpp:220)
-      double S[4], Si[4];
-      {   // S = Hb P_zz Hb^T + R
-        const double* pz = pzz + 4 * (g & 1);
-        const double p00 = pz[0], p01 = pz[1], p10 = pz[2], p11 = pz[3];
-        const double w00 = p00 * h00 + p01 * h01, w01 = p00 * h10 + p01 * h11;      // W rows j0, j0+1
-        const double w10 = p10 * h00 + p11 * h01, w11 = p10 * h10 + p11 * h11;
-        S[0] = h00 * w00 + h01 * w10 + R[0];
-        S[1] = h00 * w01 + h01 * w11 + R[2];
-        S[2] = h10 * w00 + h11 * w10 + R[1];
-        S[3] = h10 * w01 + h11 * w11 + R[3];
-      }
-      inv2_fast(S, Si);
-      const double mahal = (r0 * Si[0] + r1 * Si[2]) * r0 + (r0 * Si[1] + r1 * Si[3]) * r1;   // vi_ekf_meas.cpp:234
-      if (mahal > 9.0) {                                   // gate (:235-239): returns before fix_depth
+      double Si[4];
+      const double* pz = pzz + 4 * (g & 1);
+      const double mahal = feat_innovation(Hb, pz[0], pz[1], pz[2], pz[3], R, r0, r1, Si);   // vi_ekf_meas.cpp:230-234
+      if (mahal > kGateMahal) {                                   // gate (:235-239): returns before fix_depth
         if (res && tid == 0) *res = 1;
         if (i < nact) *reinterpret_cast<double2*>(Wp + i * BLD + 2 * g) = make_double2(0.0, 0.0);
         publish_pzz(g + 1);
@@ -1041,6 +1012,66 @@ __device__ __forceinline__ void small_inverse_dev(int r, const double* S, double
     }
 }
 
+// the models that measure a feature: they take a feature slot (QZETA, FEAT, DEPTH, INV_DEPTH)
+__device__ __forceinline__ bool meas_needs_slot(int type) {
+  return type == MT_QZETA || type == MT_FEAT || type == MT_DEPTH || type == MT_INV_DEPTH;
+}
+
+// The reference's measurement models (src/vi_ekf/vi_ekf_meas.cpp:281-386): zhat = h(x) and the non-zero columns of H -- at most six
+// (`cols`, their number `nc`), Hc [3][6] row-major = the entries of H in those columns.  One lane; xs = the filter's state.
+__device__ __forceinline__ void meas_model(int type, const double* xs, int slot, const DevParams& prm, double* zhat, int* cols,
+                                           double* Hc, int& nc) {
+  nc = 0;
+  for (int i = 0; i < 18; i++) Hc[i] = 0.0;
+  auto col = [&](int c) { cols[nc] = c; return nc++; };
+  if (type == MT_ACC) {                                       // vi_ekf_meas.cpp:281-306
+    if (prm.use_drag_term) {
+      const double mu = xs[xMU];
+      zhat[0] = -mu * xs[xVEL] + xs[xB_A]; zhat[1] = -mu * xs[xVEL + 1] + xs[xB_A + 1];
+      int c;
+      c = col(dxVEL); Hc[0 * 6 + c] = -mu;  c = col(dxVEL + 1); Hc[1 * 6 + c] = -mu;
+      c = col(dxB_A); Hc[0 * 6 + c] = 1.0;  c = col(dxB_A + 1); Hc[1 * 6 + c] = 1.0;
+      c = col(dxMU); Hc[0 * 6 + c] = -xs[xVEL]; Hc[1 * 6 + c] = -xs[xVEL + 1];
+    } else {
+      const double g[3] = {0.0, 0.0, kGravity}; double gB[3], ng[3], Sk[9];
+      q_rotp(xs + xATT, g, gB);
+      for (int i = 0; i < 3; i++) { zhat[i] = xs[xB_A + i] - gB[i]; ng[i] = -1.0 * gB[i]; }
+      skew3(ng, Sk);
+      for (int j = 0; j < 3; j++) { const int c = col(dxATT + j); for (int i = 0; i < 3; i++) Hc[i * 6 + c] = Sk[i * 3 + j]; }
+      for (int j = 0; j < 3; j++) { const int c = col(dxB_A + j); Hc[j * 6 + c] = 1.0; }
+    }
+  } else if (type == MT_ALT) { zhat[0] = -xs[xPOS + 2]; const int c = col(dxPOS + 2); Hc[c] = -1.0; }
+  else if (type == MT_ATT) { for (int i = 0; i < 4; i++) zhat[i] = xs[xATT + i]; for (int j = 0; j < 3; j++) { const int c = col(dxATT + j); Hc[j * 6 + c] = 1.0; } }
+  else if (type == MT_POS) { for (int j = 0; j < 3; j++) { zhat[j] = xs[xPOS + j]; const int c = col(dxPOS + j); Hc[j * 6 + c] = 1.0; } }
+  else if (type == MT_VEL) { for (int j = 0; j < 3; j++) { zhat[j] = xs[xVEL + j]; const int c = col(dxVEL + j); Hc[j * 6 + c] = 1.0; } }
+  else if (type == MT_QZETA) { for (int i = 0; i < 4; i++) zhat[i] = xs[xZ + 5 * slot + i]; for (int j = 0; j < 2; j++) { const int c = col(dxZ + 3 * slot + j); Hc[j * 6 + c] = 1.0; } }
+  else if (type == MT_FEAT) {
+    double Hb[4]; h_feat(xs + xZ + 5 * slot, prm, zhat, Hb);
+    for (int j = 0; j < 2; j++) { const int c = col(dxZ + 3 * slot + j); Hc[0 * 6 + c] = Hb[0 * 2 + j]; Hc[1 * 6 + c] = Hb[1 * 2 + j]; }
+  } else if (type == MT_DEPTH) { const double rho = xs[xZ + 5 * slot + 4]; zhat[0] = 1.0 / rho; const int c = col(dxZ + 3 * slot + 2); Hc[c] = -1.0 / (rho * rho); }
+  else if (type == MT_INV_DEPTH) { zhat[0] = xs[xZ + 5 * slot + 4]; const int c = col(dxZ + 3 * slot + 2); Hc[c] = 1.0; }
+}
+
+// residual z [-] zhat of a model (vi_ekf_meas.cpp:209-220): a quaternion measurement by its boxminus, the others subtract
+__device__ __forceinline__ void meas_residual(int type, const double* z, const double* zhat, int zdim, double* r3) {
+  if (type == MT_QZETA) q_feat_boxminus_dev(z, zhat, r3);           // :210-213
+  else if (type == MT_ATT) q_boxminus_dev(z, zhat, r3);             // :214-217
+  else for (int i = 0; i < zdim && i < 3; i++) r3[i] = z[i] - zhat[i];
+}
+
+// x1 [-] x2 of the body state into o[0..15] and of one feature into o3[0..2] (vi_ekf_helper.cpp:100-111)
+__device__ __forceinline__ void body_boxminus_dev(const double* x1, const double* x2, double* o) {
+  for (int i = 0; i < 6; i++) o[dxPOS + i] = x1[xPOS + i] - x2[xPOS + i];
+  double d3[3];
+  q_boxminus_dev(x1 + xATT, x2 + xATT, d3);
+  for (int i = 0; i < 3; i++) o[dxATT + i] = d3[i];
+  for (int i = 0; i < 7; i++) o[dxB_A + i] = x1[xB_A + i] - x2[xB_A + i];
+}
+__device__ __forceinline__ void feat_boxminus_dev(const double* f1, const double* f2, double* o3) {
+  q_feat_boxminus_dev(f1, f2, o3);
+  o3[2] = f1[4] - f2[4];
+}
+
 // ------------------------------------------------------------------------------------------------
 // Read-only evaluations for the log writer (src/vi_ekf/vi_ekf_log.cpp): what the reference records next to a propagate
 // (xdot = dx_ of VIEKF::dynamics, vi_ekf_dyn.cpp:6-134; the diagonal of P) and next to an update (zhat = h(x),
@@ -1094,26 +1125,11 @@ __global__ void k_eval_h(StreamArgs a, int type, const int* __restrict__ slot_al
   const DevParams& prm = *a.dp;
   const double nan = __longlong_as_double(0x7ff8000000000000LL);
   double zhat[4] = {nan, nan, nan, nan};
-  const bool needs_slot = type == 5 || type == 6 || type == 8 || type == 9;   // QZETA, FEAT, DEPTH, INV_DEPTH
+  const bool needs_slot = meas_needs_slot(type);
   const int slot = (needs_slot && slot_all) ? slot_all[b] : 0;
-  if (!needs_slot || (slot >= 0 && slot < a.len[b])) {
-    if (type == 0) {                                          // ACC, vi_ekf_meas.cpp:281-306
-      if (prm.use_drag_term) {
-        const double mu = xs[xMU];
-        zhat[0] = -mu * xs[xVEL] + xs[xB_A]; zhat[1] = -mu * xs[xVEL + 1] + xs[xB_A + 1];
-      } else {
-        const double g[3] = {0.0, 0.0, kGravity}; double gB[3];
-        q_rotp(xs + xATT, g, gB);
-        for (int i = 0; i < 3; i++) zhat[i] = xs[xB_A + i] - gB[i];
-      }
-    } else if (type == 1) zhat[0] = -xs[xPOS + 2];            // ALT
-    else if (type == 2) { for (int i = 0; i < 4; i++) zhat[i] = xs[xATT + i]; }
-    else if (type == 3) { for (int i = 0; i < 3; i++) zhat[i] = xs[xPOS + i]; }
-    else if (type == 4) { for (int i = 0; i < 3; i++) zhat[i] = xs[xVEL + i]; }
-    else if (type == 5) { for (int i = 0; i < 4; i++) zhat[i] = xs[xZ + 5 * slot + i]; }
-    else if (type == 6) { double Hb[4], zh[2]; h_feat(xs + xZ + 5 * slot, prm, zh, Hb); zhat[0] = zh[0]; zhat[1] = zh[1]; }
-    else if (type == 8) zhat[0] = 1.0 / xs[xZ + 5 * slot + 4];
-    else if (type == 9) zhat[0] = xs[xZ + 5 * slot + 4];
+  if (!needs_slot || (slot >= 0 && slot < a.len[b])) {   // (meas_model writes only the entries its model uses)
+    int cols[6], nc; double Hc[18];
+    meas_model(type, xs, slot, prm, zhat, cols, Hc, nc);
   }
   for (int i = 0; i < 4; i++) out[(long)b * 4 + i] = zhat[i];
 }
@@ -1217,41 +1233,6 @@ __global__ void k_cov_block(StreamArgs a, int r0, int c0, int nr, int nc, double
 }
 #endif
 
-// The reference's measurement models (src/vi_ekf/vi_ekf_meas.cpp:281-386): zhat = h(x) and the non-zero columns of H -- at most six
-// (`cols`, their number `nc`), Hc [3][6] row-major = the entries of H in those columns.  One lane; xs = the filter's state.
-__device__ __forceinline__ void meas_model(int type, const double* xs, int slot, const DevParams& prm, double* zhat, int* cols,
-                                           double* Hc, int& nc) {
-  nc = 0;
-  for (int i = 0; i < 18; i++) Hc[i] = 0.0;
-  auto col = [&](int c) { cols[nc] = c; return nc++; };
-  if (type == MT_ACC) {                                       // vi_ekf_meas.cpp:281-306
-    if (prm.use_drag_term) {
-      const double mu = xs[xMU];
-      zhat[0] = -mu * xs[xVEL] + xs[xB_A]; zhat[1] = -mu * xs[xVEL + 1] + xs[xB_A + 1];
-      int c;
-      c = col(dxVEL); Hc[0 * 6 + c] = -mu;  c = col(dxVEL + 1); Hc[1 * 6 + c] = -mu;
-      c = col(dxB_A); Hc[0 * 6 + c] = 1.0;  c = col(dxB_A + 1); Hc[1 * 6 + c] = 1.0;
-      c = col(dxMU); Hc[0 * 6 + c] = -xs[xVEL]; Hc[1 * 6 + c] = -xs[xVEL + 1];
-    } else {
-      const double g[3] = {0.0, 0.0, kGravity}; double gB[3], ng[3], Sk[9];
-      q_rotp(xs + xATT, g, gB);
-      for (int i = 0; i < 3; i++) { zhat[i] = xs[xB_A + i] - gB[i]; ng[i] = -1.0 * gB[i]; }
-      skew3(ng, Sk);
-      for (int j = 0; j < 3; j++) { const int c = col(dxATT + j); for (int i = 0; i < 3; i++) Hc[i * 6 + c] = Sk[i * 3 + j]; }
-      for (int j = 0; j < 3; j++) { const int c = col(dxB_A + j); Hc[j * 6 + c] = 1.0; }
-    }
-  } else if (type == MT_ALT) { zhat[0] = -xs[xPOS + 2]; const int c = col(dxPOS + 2); Hc[c] = -1.0; }
-  else if (type == MT_ATT) { for (int i = 0; i < 4; i++) zhat[i] = xs[xATT + i]; for (int j = 0; j < 3; j++) { const int c = col(dxATT + j); Hc[j * 6 + c] = 1.0; } }
-  else if (type == MT_POS) { for (int j = 0; j < 3; j++) { zhat[j] = xs[xPOS + j]; const int c = col(dxPOS + j); Hc[j * 6 + c] = 1.0; } }
-  else if (type == MT_VEL) { for (int j = 0; j < 3; j++) { zhat[j] = xs[xVEL + j]; const int c = col(dxVEL + j); Hc[j * 6 + c] = 1.0; } }
-  else if (type == MT_QZETA) { for (int i = 0; i < 4; i++) zhat[i] = xs[xZ + 5 * slot + i]; for (int j = 0; j < 2; j++) { const int c = col(dxZ + 3 * slot + j); Hc[j * 6 + c] = 1.0; } }
-  else if (type == MT_FEAT) {
-    double Hb[4]; h_feat(xs + xZ + 5 * slot, prm, zhat, Hb);
-    for (int j = 0; j < 2; j++) { const int c = col(dxZ + 3 * slot + j); Hc[0 * 6 + c] = Hb[0 * 2 + j]; Hc[1 * 6 + c] = Hb[1 * 2 + j]; }
-  } else if (type == MT_DEPTH) { const double rho = xs[xZ + 5 * slot + 4]; zhat[0] = 1.0 / rho; const int c = col(dxZ + 3 * slot + 2); Hc[c] = -1.0 / (rho * rho); }
-  else if (type == MT_INV_DEPTH) { zhat[0] = xs[xZ + 5 * slot + 4]; const int c = col(dxZ + 3 * slot + 2); Hc[c] = 1.0; }
-}
-
 template <int T>
 __global__ __launch_bounds__(T) void k_update_generic(StreamArgs a, int type, int zdim, int rdim,
                                                       const double* __restrict__ z_all, const int* __restrict__ slot_all,
@@ -1277,8 +1258,7 @@ __global__ __launch_bounds__(T) void k_update_generic(StreamArgs a, int type, in
   int* res_out = result_all ? &result_all[b] : nullptr;
   if (active_all && active_all[b] == 2) { if (res_out && tid == 0) *res_out = -1; return; }   // this filter skips the call
   unsigned flag = 0;
-  const bool needs_slot = type == MT_QZETA || type == MT_FEAT || type == MT_DEPTH || type == MT_INV_DEPTH;
-  if (needs_slot && (slot < 0 || slot >= len)) { if (res_out && tid == 0) *res_out = (slot < 0) ? -1 : 3; return; }
+  if (meas_needs_slot(type) && (slot < 0 || slot >= len)) { if (res_out && tid == 0) *res_out = (slot < 0) ? -1 : 3; return; }
   const double* z = z_all + (long)b * zdim;
   {
     bool isnan_ = false;
@@ -1292,9 +1272,7 @@ __global__ __launch_bounds__(T) void k_update_generic(StreamArgs a, int type, in
   if (tid == 0) {   // measurement model: zhat, the non-zero columns of H, residual
     int cols[6]; double Hc[18]; int nc = 0; double zhat[4] = {0, 0, 0, 0}; double r3[3] = {0, 0, 0};
     meas_model(type, xs, slot, prm, zhat, cols, Hc, nc);
-    if (type == MT_QZETA) q_feat_boxminus_dev(z, zhat, r3);           // :210-213
-    else if (type == MT_ATT) q_boxminus_dev(z, zhat, r3);             // :214-217
-    else for (int i = 0; i < zdim && i < 3; i++) r3[i] = z[i] - zhat[i];
+    meas_residual(type, z, zhat, zdim, r3);
     for (int i = 0; i < 6; i++) sm[i] = (i < nc) ? (double)cols[i] : 0.0;
     for (int i = 0; i < 18; i++) sm[6 + i] = Hc[i];
     sm[24] = r3[0]; sm[25] = r3[1]; sm[26] = r3[2]; sm[27] = (double)nc;
@@ -1332,7 +1310,7 @@ __global__ __launch_bounds__(T) void k_update_generic(StreamArgs a, int type, in
     double mahal = 0.0;
     for (int q = 0; q < rdim; q++) { double t = 0.0; for (int p = 0; p < rdim; p++) t += sm[24 + p] * Si[p * rdim + q]; mahal += t * sm[24 + q]; }
     for (int i = 0; i < 9; i++) sm[28 + i] = (i < rdim * rdim) ? Si[i] : 0.0;
-    sm[37] = (mahal > 9.0) ? 1.0 : 0.0;   // :234-239
+    sm[37] = (mahal > kGateMahal) ? 1.0 : 0.0;   // :234-239
   }
   __syncthreads();
   if (sm[37] != 0.0) { if (res_out && tid == 0) *res_out = 1; return; }   // gated: returns before fix_depth

@@ -637,16 +637,7 @@ __global__ __launch_bounds__(T) void k_update_feat_panelsvc(StreamArgs a, const 
 
   // fix_depth (vi_ekf_helper.cpp:128-156) of one feature: rho and its P(rho, rho), both in the caller's registers
   auto fix_depth_v = [&](double& rho, double& prr) {
-    if (rho != rho) { rho = rho_reset; flag |= FLAG_NAN; }
-    if (rho < 0.0) {
-      const double err = rho_reset - rho;
-      prr += err * err;
-      rho = rho_reset;
-      flag |= FLAG_NEGDEPTH;
-    } else if (rho > 1e2) {
-      prr = p0rr;
-      rho = rho_reset;
-    }
+    fix_depth_rule(rho, rho_reset, flag, [&](double e2) { prr += e2; }, [&] { prr = p0rr; });
   };
   auto in_set = [](int f, unsigned long long s0, unsigned long long s1, unsigned long long s2) {
     return ((f < 64 ? s0 : (f < 128 ? s1 : s2)) >> (f & 63)) & 1ull;
@@ -838,18 +829,9 @@ __global__ __launch_bounds__(T) void k_update_feat_panelsvc(StreamArgs a, const 
             const double r0 = wz[2 * wi] - zhat[0], r1 = wz[2 * wi + 1] - zhat[1];
             const double* R = wR + 4 * wi;
             const double p00 = psv_rl(sp[2 * g], L0), p01 = psv_rl(sp[2 * g + 1], L0), p10 = psv_rl(sp[2 * g], L0 + 1), p11 = psv_rl(sp[2 * g + 1], L0 + 1);
-            double S[4], Si[4];
-            {
-              const double w00 = p00 * hb[0] + p01 * hb[1], w01 = p00 * hb[2] + p01 * hb[3];
-              const double w10 = p10 * hb[0] + p11 * hb[1], w11 = p10 * hb[2] + p11 * hb[3];
-              S[0] = hb[0] * w00 + hb[1] * w10 + R[0];
-              S[1] = hb[0] * w01 + hb[1] * w11 + R[2];
-              S[2] = hb[2] * w00 + hb[3] * w10 + R[1];
-              S[3] = hb[2] * w01 + hb[3] * w11 + R[3];
-            }
-            inv2_fast(S, Si);
-            const double mahal = (r0 * Si[0] + r1 * Si[2]) * r0 + (r0 * Si[1] + r1 * Si[3]) * r1;   // :234
-            const bool gate = mahal > 9.0;
+            double Si[4];
+            const double mahal = feat_innovation(hb, p00, p01, p10, p11, R, r0, r1, Si);   // :230-234
+            const bool gate = mahal > kGateMahal;
             if (hb[0] != hb[0] || hb[1] != hb[1] || hb[2] != hb[2] || hb[3] != hb[3]) sbad = 1;
             if (lane == 0) {
               double* ml = mail + 12 * g;

@@ -106,19 +106,8 @@ __device__ RES_INLINE void res_feature_expand_row(int f, int r, double dt, doubl
 __device__ RES_INLINE void res_fix_depth(double* xf, const DevParams* p, double* fixadd_slot, double* fixset_slot,
                                          double* fixany, unsigned* flag) {
   double rho = xf[4];
-  const double reset = 1.0 / (2.0 * p->min_depth);
-  if (rho != rho) { rho = reset; *flag |= FLAG_NAN; }
-  if (rho < 0.0) {
-    const double err = reset - rho;
-    *fixadd_slot = err * err;
-    *fixany = 1.0;
-    rho = reset;
-    *flag |= FLAG_NEGDEPTH;
-  } else if (rho > 1e2) {
-    *fixset_slot = 1.0;
-    *fixany = 1.0;
-    rho = reset;
-  }
+  fix_depth_rule(rho, 1.0 / (2.0 * p->min_depth), *flag, [&](double e2) { *fixadd_slot = e2; *fixany = 1.0; },
+                 [&] { *fixset_slot = 1.0; *fixany = 1.0; });
   xf[4] = rho;
 }
 

@@ -148,23 +148,15 @@ __device__ __forceinline__ void res_service(const StreamArgs& a, const ResShared
   // prediction + innovation of measurement mm, whose feature is lane `src` (wave-uniform): EVERY lane runs the arithmetic
   // on its own registers (no divergence; the other lanes' results are discarded), lane src's values are broadcast
   auto predict = [&](const double* t1, const double* t2, const double* zt, int mm, int src, Meas& o) {
-    double zhat[2], Hb[4], Sm[4], Si[4];
+    double zhat[2], Hb[4], Si[4];
     h_feat_frame(t1, t2, zt, prm, zhat, Hb);
     const double2 zn = lds_ld2(S.mz + 2 * mm);
-    const double* R = S.mR + 4 * mm;
     const double r0 = zn.x - zhat[0], r1 = zn.y - zhat[1];
-    const double w00 = pf00 * Hb[0] + pf01 * Hb[1], w01 = pf00 * Hb[2] + pf01 * Hb[3];   // (P_zz Hb^T)
-    const double w10 = pf10 * Hb[0] + pf11 * Hb[1], w11 = pf10 * Hb[2] + pf11 * Hb[3];
-    Sm[0] = Hb[0] * w00 + Hb[1] * w10 + R[0];
-    Sm[1] = Hb[0] * w01 + Hb[1] * w11 + R[2];
-    Sm[2] = Hb[2] * w00 + Hb[3] * w10 + R[1];
-    Sm[3] = Hb[2] * w01 + Hb[3] * w11 + R[3];
-    inv2_fast(Sm, Si);
-    const double mahal = (r0 * Si[0] + r1 * Si[2]) * r0 + (r0 * Si[1] + r1 * Si[3]) * r1;   // vi_ekf_meas.cpp:234
+    const double mahal = feat_innovation(Hb, pf00, pf01, pf10, pf11, S.mR + 4 * mm, r0, r1, Si);   // vi_ekf_meas.cpp:230-234
     o.h0 = bcast(Hb[0], src); o.h1 = bcast(Hb[1], src); o.h2 = bcast(Hb[2], src); o.h3 = bcast(Hb[3], src);
     o.r0 = bcast(r0, src); o.r1 = bcast(r1, src);
     o.s0 = bcast(Si[0], src); o.s1 = bcast(Si[1], src); o.s2 = bcast(Si[2], src); o.s3 = bcast(Si[3], src);
-    o.gate = bcast((mahal > 9.0) ? 1.0 : 0.0, src);                                       // gate (:235-239)
+    o.gate = bcast((mahal > kGateMahal) ? 1.0 : 0.0, src);                                       // gate (:235-239)
   };
   // this lane's quaternion and linear state live in registers for the whole loop (written back once at the end)
   double qn[4] = {qptr[0], qptr[1], qptr[2], qptr[3]};
@@ -173,7 +165,7 @@ __device__ __forceinline__ void res_service(const StreamArgs& a, const ResShared
   // correction's T_zeta both use it, so it is computed once per update
   double f1[3], f2[3], fz[3];
   bearing_frame_fast(qn, f1, f2, fz);
-  const double sgn = isatt ? -1.0 : 1.0;   // q (x) e instead of e (x) q flips the cross term only
+  const double sgn = isatt ? -1.0 : 1.0;   // the attitude lane right-multiplies (q_step_signed)
   // Gain rows of a measurement for ALL n rows (three per lane) from its raw column pair pr (this lane's rows):
   //   W_i = P[i, j0:j0+2] Hb^T,  K_i = W_i S^-1   (vi_ekf_meas.cpp:241).
   // Also leaves the NaN guard (:247; a NaN in H makes every K row NaN, so testing K covers the H test) and the gate verdict
@@ -323,15 +315,7 @@ __device__ __forceinline__ void res_service(const StreamArgs& a, const ResShared
       // x <- x [+] dx  (vi_ekf_helper.cpp:88-98): bearing  exp(T_z d) (x) q ;  attitude  q (x) exp(d) ;  the rest adds.
       // The corrected quaternion / inverse depth stay in registers for fix_depth and the next prediction.
       auto correct = [&]() {
-        double e[4];
-        q_exp_fast(v, e);
-        // e (x) q  and  q (x) e  share every term but the sign of the cross product (src/quat.cpp:304-312)
-        const double ex = sgn * e[1], ey = sgn * e[2], ez = sgn * e[3];
-        const double o0 = e[0] * qn[0] - e[1] * qn[1] - e[2] * qn[2] - e[3] * qn[3];
-        const double o1 = e[0] * qn[1] + qn[0] * e[1] + (ey * qn[3] - ez * qn[2]);
-        const double o2 = e[0] * qn[2] + qn[0] * e[2] + (ez * qn[1] - ex * qn[3]);
-        const double o3 = e[0] * qn[3] + qn[0] * e[3] + (ex * qn[2] - ey * qn[1]);
-        qn[0] = o0; qn[1] = o1; qn[2] = o2; qn[3] = o3;
+        q_step_signed(v, sgn, qn);
         bearing_frame_fast(qn, f1, f2, fz);
         lin += isfeat ? dv2 : dv0;
         // this lane's copy of P_zz follows the sweep:  P_rs -= Lambda_rs (K_r . W_s)   (vi_ekf_meas.cpp:256-257)
@@ -380,15 +364,7 @@ __device__ __forceinline__ void res_service(const StreamArgs& a, const ResShared
       // x <- x [+] dx  (vi_ekf_helper.cpp:88-98): bearing  exp(T_z d) (x) q ;  attitude  q (x) exp(d) ;  the rest adds.
       // The corrected quaternion / inverse depth stay in registers for fix_depth and the next prediction.
       if (corr) {
-        double e[4];
-        q_exp_fast(v, e);
-        // e (x) q  and  q (x) e  share every term but the sign of the cross product (src/quat.cpp:304-312)
-        const double ex = sgn * e[1], ey = sgn * e[2], ez = sgn * e[3];
-        const double o0 = e[0] * qn[0] - e[1] * qn[1] - e[2] * qn[2] - e[3] * qn[3];
-        const double o1 = e[0] * qn[1] + qn[0] * e[1] + (ey * qn[3] - ez * qn[2]);
-        const double o2 = e[0] * qn[2] + qn[0] * e[2] + (ez * qn[1] - ex * qn[3]);
-        const double o3 = e[0] * qn[3] + qn[0] * e[3] + (ex * qn[2] - ey * qn[1]);
-        qn[0] = o0; qn[1] = o1; qn[2] = o2; qn[3] = o3;
+        q_step_signed(v, sgn, qn);
         bearing_frame_fast(qn, f1, f2, fz);
         lin += isfeat ? dv2 : dv0;
         // this lane's copy of P_zz follows the sweep:  P_rs -= Lambda_rs (K_r . W_s)   (vi_ekf_meas.cpp:256-257)
@@ -408,20 +384,8 @@ __device__ __forceinline__ void res_service(const StreamArgs& a, const ResShared
     if (__any(odd_depth)) {
       if (odd_depth) {
         VIEKF_COLD_BEGIN();
-        double rho = lin;
-        if (rho != rho) { rho = rho_reset; flag |= FLAG_NAN; }
-        if (rho < 0.0) {
-          const double err = rho_reset - rho;
-          S.fixadd[par * N + fid] = err * err;
-          sm[FIXW + par] = 1.0;
-          rho = rho_reset;
-          flag |= FLAG_NEGDEPTH;
-        } else if (rho > 1e2) {
-          S.fixset[par * N + fid] = 1.0;
-          sm[FIXW + par] = 1.0;
-          rho = rho_reset;
-        }
-        lin = rho;
+        fix_depth_rule(lin, rho_reset, flag, [&](double e2) { S.fixadd[par * N + fid] = e2; sm[FIXW + par] = 1.0; },
+                       [&] { S.fixset[par * N + fid] = 1.0; sm[FIXW + par] = 1.0; });
         VIEKF_COLD_END();
       }
     }

@@ -186,6 +186,9 @@ struct viekf_seq {
 
 namespace {
 
+// the measurement types that name a feature: their updates take a slot list (the device side's meas_needs_slot, by the public ABI)
+bool meas_needs_slot(int type) { return type == VIEKF_QZETA || type == VIEKF_FEAT || type == VIEKF_DEPTH || type == VIEKF_INV_DEPTH; }
+
 // vi_ekf_helper.cpp:114-125 (a linear std::find there; a frame of 50 features on 1024 filters asks 100,000 times per frame: table)
 int local_id(const viekf_seq* s, int b, int gid) {
   const auto& m = s->slot_of[b];
@@ -435,7 +438,7 @@ int update_entry(viekf_seq* s, SeqMeas& m, std::vector<int32_t>& res) {   // VIE
   m.handled = true;                                                // :198
   res.assign(B, VIEKF_MEAS_SKIPPED);
   std::vector<int32_t> slot(B, -1);
-  const bool needs_slot = m.type == VIEKF_QZETA || m.type == VIEKF_FEAT || m.type == VIEKF_DEPTH || m.type == VIEKF_INV_DEPTH;
+  const bool needs_slot = meas_needs_slot(m.type);
   std::vector<uint8_t> act(B);
   for (int b = 0; b < B; b++) {
     if (needs_slot) slot[b] = m.present[b] ? local_id(s, b, m.id[b]) : -1;
@@ -745,7 +748,7 @@ int run_ops(viekf_seq* s, std::vector<std::vector<SeqOp>>& ops, std::vector<std:
       std::vector<double> z((size_t)B * zdim, 0.0), R((size_t)B * rdim * rdim, 0.0);
       std::vector<int32_t> sl(B, -1), res(B, VIEKF_MEAS_SKIPPED);
       std::vector<uint8_t> act(B, 2);                              // 2 = this filter takes no part
-      const bool needs_slot = type == VIEKF_QZETA || type == VIEKF_FEAT || type == VIEKF_DEPTH || type == VIEKF_INV_DEPTH;
+      const bool needs_slot = meas_needs_slot(type);
       for (int b = 0; b < B; b++) {
         if (!mask[b]) continue;
         const FMeas& m = ops[b][head[b]].meas[0];

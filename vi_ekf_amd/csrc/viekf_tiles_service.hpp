@@ -124,19 +124,11 @@ __device__ __forceinline__ void tile_service(const StreamArgs& a, const TileShar
   // own registers (no divergence), lane src's values are broadcast.  h_feat vi_ekf_meas.cpp:354-367; S, gate :230-239;
   //   G = Hb^T S^-1 Hb  (K W^T = C G C^T),   g_r = Hb^T S^-1 r  (K r = C g_r);   skip = gated (1) or a NaN in G / g_r (2: :247)
   auto predict = [&](const double* t1, const double* t2, const double* zt, int mm, int src, Meas& o) {
-    double zhat[2], Hb[4], Sm[4], Si[4];
+    double zhat[2], Hb[4], Si[4];
     h_feat_frame(t1, t2, zt, prm, zhat, Hb);
     const double2 zn = lds_ld2(S.mz + 2 * mm);
-    const double* R = S.mR + 4 * mm;
     const double r0 = zn.x - zhat[0], r1 = zn.y - zhat[1];
-    const double w00 = pf00 * Hb[0] + pf01 * Hb[1], w01 = pf00 * Hb[2] + pf01 * Hb[3];   // (P_zz Hb^T)
-    const double w10 = pf01 * Hb[0] + pf11 * Hb[1], w11 = pf01 * Hb[2] + pf11 * Hb[3];
-    Sm[0] = Hb[0] * w00 + Hb[1] * w10 + R[0];
-    Sm[1] = Hb[0] * w01 + Hb[1] * w11 + R[2];
-    Sm[2] = Hb[2] * w00 + Hb[3] * w10 + R[1];
-    Sm[3] = Hb[2] * w01 + Hb[3] * w11 + R[3];
-    inv2_fast(Sm, Si);
-    const double mahal = (r0 * Si[0] + r1 * Si[2]) * r0 + (r0 * Si[1] + r1 * Si[3]) * r1;   // vi_ekf_meas.cpp:234
+    const double mahal = feat_innovation(Hb, pf00, pf01, pf01, pf11, S.mR + 4 * mm, r0, r1, Si);   // vi_ekf_meas.cpp:230-234
     // M = S^-1 Hb (2x2), G = Hb^T M, g_r = Hb^T (S^-1 r)
     const double m00 = Si[0] * Hb[0] + Si[1] * Hb[2], m01 = Si[0] * Hb[1] + Si[1] * Hb[3];
     const double m10 = Si[2] * Hb[0] + Si[3] * Hb[2], m11 = Si[2] * Hb[1] + Si[3] * Hb[3];
@@ -144,7 +136,7 @@ __device__ __forceinline__ void tile_service(const StreamArgs& a, const TileShar
     const double s0 = Si[0] * r0 + Si[1] * r1, s1 = Si[2] * r0 + Si[3] * r1;
     const double gr0 = Hb[0] * s0 + Hb[2] * s1, gr1 = Hb[1] * s0 + Hb[3] * s1;
     const double chk = (g00 + g01) + (g11 + gr0) + gr1;
-    const double skip = (chk != chk) ? 2.0 : ((mahal > 9.0) ? 1.0 : 0.0);                 // NaN guard first: a NaN never gates
+    const double skip = (chk != chk) ? 2.0 : ((mahal > kGateMahal) ? 1.0 : 0.0);                 // NaN guard first: a NaN never gates
     o.g00 = bcast(g00, src); o.g01 = bcast(g01, src); o.g11 = bcast(g11, src);
     o.gr0 = bcast(gr0, src); o.gr1 = bcast(gr1, src); o.skip = bcast(skip, src);
   };
@@ -159,7 +151,7 @@ __device__ __forceinline__ void tile_service(const StreamArgs& a, const TileShar
   double lin = *linptr;
   double f1[3], f2[3], fz[3];
   bearing_frame_fast(qn, f1, f2, fz);
-  const double sgn = isatt ? -1.0 : 1.0;   // q (x) e instead of e (x) q flips the cross term only
+  const double sgn = isatt ? -1.0 : 1.0;   // the attitude lane right-multiplies (q_step_signed)
   Meas cur = {}, nxt = {};
   if (m < M) {
     predict(f1, f2, fz, m, __builtin_amdgcn_readfirstlane(S.mslot[m]), cur);
@@ -196,14 +188,7 @@ __device__ __forceinline__ void tile_service(const StreamArgs& a, const TileShar
     const bool corr = !gated && !bad && !RES_ABLATE(S, 2);
     // x <- x [+] dx  (vi_ekf_helper.cpp:88-98): bearing  exp(T_z d) (x) q ;  attitude  q (x) exp(d) ;  the rest adds
     if (corr) {
-      double e[4];
-      q_exp_fast(v, e);
-      const double ex = sgn * e[1], ey = sgn * e[2], ez = sgn * e[3];
-      const double o0 = e[0] * qn[0] - e[1] * qn[1] - e[2] * qn[2] - e[3] * qn[3];
-      const double o1 = e[0] * qn[1] + qn[0] * e[1] + (ey * qn[3] - ez * qn[2]);
-      const double o2 = e[0] * qn[2] + qn[0] * e[2] + (ez * qn[1] - ex * qn[3]);
-      const double o3 = e[0] * qn[3] + qn[0] * e[3] + (ex * qn[2] - ey * qn[1]);
-      qn[0] = o0; qn[1] = o1; qn[2] = o2; qn[3] = o3;
+      q_step_signed(v, sgn, qn);
       bearing_frame_fast(qn, f1, f2, fz);
       lin += isfeat ? dv2 : dv0;
       // this lane's copy of P_zz follows the sweep:  P_zz -= Lambda o (C_z G C_z^T)   (vi_ekf_meas.cpp:256-257)
@@ -220,20 +205,8 @@ __device__ __forceinline__ void tile_service(const StreamArgs& a, const TileShar
     const bool odd_depth = !gated && isfeat && fid < len && !(lin >= 0.0 && lin <= 1e2);
     if (__any(odd_depth)) {
       if (odd_depth) {
-        double rho = lin;
-        if (rho != rho) { rho = rho_reset; flag |= FLAG_NAN; }
-        if (rho < 0.0) {
-          const double err = rho_reset - rho;
-          S.fixadd[par * N + fid] = err * err;
-          sm[40 + par] = 1.0;
-          rho = rho_reset;
-          flag |= FLAG_NEGDEPTH;
-        } else if (rho > 1e2) {
-          S.fixset[par * N + fid] = 1.0;
-          sm[40 + par] = 1.0;
-          rho = rho_reset;
-        }
-        lin = rho;
+        fix_depth_rule(lin, rho_reset, flag, [&](double e2) { S.fixadd[par * N + fid] = e2; sm[40 + par] = 1.0; },
+                       [&] { S.fixset[par * N + fid] = 1.0; sm[40 + par] = 1.0; });
       }
     }
     if (slot_next >= 0) {   // next measurement, from registers
