@@ -212,6 +212,36 @@ def test_ring_routes():
     assert "P packed" in a.desc
 
 
+def test_per_filter_mode_entered_from_packed_buffers():
+    """per-filter ring copies and live slots entered while a ring slot AND the batch's own buffers hold packed images: every
+    packed buffer is unpacked first (the slot loop of canonicalize_all), then back to whole-batch mode through a resize"""
+    B, N = 2, 12
+    L = capi.lib()
+
+    def script(r):
+        g, sc = r.g, r.sc
+        g.history_resize(4)
+        r.note(r.step(0))
+        r.note(r.step(1))
+        g.snapshot(1)                                       # a packed ring slot beside the packed live buffers
+        r.note(r.step(2))
+        live = np.array([0, 3], dtype=np.int32)
+        capi.check(L.viekf_batch_snapshot_filters(g._h, _p(live), capi.HOST))
+        g.select_filters(live)
+        dst = np.array([2, -1], dtype=np.int32)             # filter 0 advances into slot 2, filter 1 stays put
+        capi.check(L.viekf_batch_propagate_filters_to(g._h, _p(sc["u"][3]), _p(sc["dt"]), _p(dst), capi.HOST))
+        r.read(g.update_feat(r.z[3], sc["slot"], sc["R"]).copy())
+        g.history_resize(0)                                 # every filter's live slot goes home: whole-batch mode again
+        g.history_resize(4)
+        r.read(r.step(4))
+        g.snapshot(1)
+        g.restore(1)
+        r.read(r.step(5))
+
+    a, _ = both(script, B, N, inst=I_2_1, seed=29)
+    assert "P packed" in a.g.describe()
+
+
 @pytest.mark.parametrize("N,inst", [(3, None), (12, I_2_1)])
 def test_shared_clock_sequencer_with_a_delayed_frame(N, inst):
     B = 2

@@ -7,7 +7,7 @@ Every timed call follows a headline step (propagate + N feature updates in the f
 diagonal is stale, as it is for a user who asks between two frames.
   device   viekf_diag_consistency with device pointers (x_true, logdet, nees, whitened, info all on the device), timed with
            device events around each call on the batch's stream; the step before it is outside the timed interval.
-  host     viekf_batch_get_state(P) to host memory -- which first mirrors the lower triangle up (ensure_full_P) -- then
+  host     viekf_batch_get_state(P) to host memory -- which first mirrors the lower triangle up (require_P) -- then
            numpy.linalg.cholesky / solve over the batch and the sums, under the process's thread quota; timed with a host
            clock (the copy ends in a synchronise).  e comes from viekf_batch_boxminus and is not counted.
   copy     the bare device-to-host copy of P (a second get_state straight after: nothing left to mirror).

@@ -11,6 +11,7 @@
 #include "../../include/viekf.h"
 #include "viekf_host.hpp"
 #include "viekf_kernels_stream.hpp"
+#include "viekf_pform.hpp"
 
 using namespace viekf;
 
@@ -32,27 +33,12 @@ struct viekf_batch {
   size_t res_lds = 0;
   DevParams dp;
   DevParams* d_dp = nullptr;
-  // P is symmetric and the hot kernels keep only its LOWER triangle current; what is above the diagonal may be stale:
-  //   0  all of P valid
-  //   2  stale above the diagonal (left by the fused kernels, the matrix-core propagate and the grouped update: all of them read
-  //      and write the lower triangle only)
-  //   3  the live P may be PACKED: not the column-major matrix but the fused kernel's own register and LDS image (ResPack,
-  //      viekf_instance_rows.hpp), left by a fused launch for the next one -- whole-batch mode only, never under per-filter
-  //      live slots or a participation mask (the batch would end up mixed)
-  // ensure_full_P(b, tolerate) brings the live P down to a level the caller can read: 3 -> 2 by unpacking (the fused kernel's
-  // own conversion launch), 2 -> 0 by mirroring the lower triangle up.  Levels are set through set_level only.
-  int upper_stale = 0;
-  int stale_ever = 0;         // the highest CANONICAL level (<= 2) any launch of this batch has left: a canonical ring slot is taken
-                              // to be that stale when it becomes (part of) the live state again
-  // Form of every buffer that can hold a whole batch's P: packed (1) or canonical (0) -- the batch's own buffers and each ring
-  // slot.  Set by whoever writes the buffer (a fused launch through P_out, ring copies, snapshot / restore), consulted when it
-  // becomes live.  Launches are uniform over the batch, so this is host state; the live buffer's entry is (upper_stale == 3).
-  unsigned char home_packed = 0;
-  std::vector<unsigned char> slot_packed;   // [hist_depth]
+  // form of P between launches, which buffer holds the live state, per-filter mode (viekf_pform.hpp); d_x / d_P follow it
+  // through point_live() below
+  PBook book;
   int tune_packed_p = 1;      // VIEKF_TUNE_PACKED_P: 0 = fused launches store canonical
   int hist_depth = 0;
-  int live_slot = -1;        // >= 0: the live (x, P) ARE this slot of the history ring (d_x / d_P point into it)
-  double *home_x = nullptr, *home_P = nullptr;   // the batch's own buffers (live state while live_slot < 0)
+  double *home_x = nullptr, *home_P = nullptr;   // the batch's own buffers (allocated by viekf_batch_create)
   double *h_x = nullptr, *h_P = nullptr;
   int* h_len = nullptr;
   unsigned char* d_active = nullptr;   // [B] participation mask of the next propagate / feature-update launches (NULL: all)
@@ -61,7 +47,6 @@ struct viekf_batch {
   int* d_ringslot = nullptr;           // [B] staging of per-filter ring slots (viekf_batch_snapshot_filters / _restore_filters)
   // per-filter live ring slots (viekf_batch_select_filters): every filter's live (x, P) is a slot of the ring of its own; d_x / d_P
   // then point at the ring's base and the kernels address filter b through smap[b] = slot_b * B + b (StreamArgs::si).
-  bool per_filter = false;
   std::vector<int32_t> live_slots;     // [B] host mirror
   int* d_smap = nullptr;               // [B] device: smap[b] = live_slots[b] * B + b, kept current in stream order by k_set_smap and by
                                        // the fused kernel itself when it stores a filter into another slot
@@ -102,9 +87,10 @@ int check_batch(const viekf_batch* b) {
   return VIEKF_OK;
 }
 
-StreamArgs make_args(const viekf_batch* b) {
+// call_mask: the participation mask of this one launch, in place of the handle's (the per-filter propagates)
+StreamArgs make_args(const viekf_batch* b, const unsigned char* call_mask = nullptr) {
   StreamArgs a;
-  a.smap = b->per_filter ? b->d_smap : nullptr;
+  a.smap = b->book.per_filter() ? b->d_smap : nullptr;
   a.smap_out = nullptr;
   a.kcount = nullptr;
   a.x =b->d_x; a.P = b->d_P; a.len = b->d_len; a.flags = b->d_flags;
@@ -113,7 +99,7 @@ StreamArgs make_args(const viekf_batch* b) {
   a.ws_stride = b->ws_stride;
   a.dp = b->d_dp;
   a.x_out = b->d_x; a.P_out = b->d_P;
-  a.active = b->active_on ? b->d_active : nullptr;
+  a.active = call_mask ? call_mask : (b->active_on ? b->d_active : nullptr);
   a.resmap = b->d_resmap;
   return a;
 }
@@ -124,27 +110,14 @@ size_t hist_nP(const viekf_batch* b) { return sizeof(double) * (size_t)b->B * b-
 double* slot_x(const viekf_batch* b, int slot) { return reinterpret_cast<double*>(reinterpret_cast<char*>(b->h_x) + hist_nx(b) * slot); }
 double* slot_P(const viekf_batch* b, int slot) { return reinterpret_cast<double*>(reinterpret_cast<char*>(b->h_P) + hist_nP(b) * slot); }
 
-// The packed / canonical entry of the buffer that holds the live P: a ring slot's or the batch's own buffers'.  Whole-batch mode
-// only: under per-filter live slots no single buffer is live, every buffer stays canonical and there is no entry (nullptr).
-unsigned char* live_form(viekf_batch* b) {
-  if (b->per_filter) return nullptr;
-  return b->live_slot >= 0 ? &b->slot_packed[(size_t)b->live_slot] : &b->home_packed;
-}
-// The one place the live level changes, in every mode: keeps the live buffer's form entry (where there is one) and stale_ever
-// with it.  Callers do not branch on per_filter.
-void set_level(viekf_batch* b, int level) {
-  b->upper_stale = level;
-  if (unsigned char* f = live_form(b)) *f = level == 3;
-  b->stale_ever = std::max(b->stale_ever, std::min(level, 2));
-}
-// A covariance is copied into and out of the ring as it stands, stale upper triangle included.  A buffer's FORM is known
-// (home_packed / slot_packed); a canonical buffer carries no level of its own: what becomes (part of) the live state again is
-// taken to be as stale as anything canonical this batch ever produced.
-void mark_restored_stale(viekf_batch* b) { b->upper_stale = std::min(2, std::max(b->stale_ever, b->upper_stale)); }
-// ... the live P now IS (a copy of) a whole-batch buffer of form `packed` (whole-batch mode: both callers refuse per-filter mode)
-void mark_live_from(viekf_batch* b, bool packed) {
-  if (packed) b->upper_stale = 3; else mark_restored_stale(b);
-  if (unsigned char* f = live_form(b)) *f = packed;
+// (x, P) of a buffer that holds a whole batch: the batch's own (PBook::kHome) or a ring slot
+double* buf_x(const viekf_batch* b, int buf) { return buf < 0 ? b->home_x : slot_x(b, buf); }
+double* buf_P(const viekf_batch* b, int buf) { return buf < 0 ? b->home_P : slot_P(b, buf); }
+// d_x / d_P follow the book: the live buffer, or the ring's base under per-filter mode.  Called after every event that moves
+// the live state (select, enter_per_filter, resized).
+void point_live(viekf_batch* b) {
+  b->d_x = b->book.per_filter() ? b->h_x : buf_x(b, b->book.live_slot());
+  b->d_P = b->book.per_filter() ? b->h_P : buf_P(b, b->book.live_slot());
 }
 
 // lambda = 1 on the bearing components, or no partial update at all: the fused kernel's unit-Lambda (ZU) instances apply

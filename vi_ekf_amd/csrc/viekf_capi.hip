@@ -133,8 +133,9 @@ int viekf_batch_create(int32_t batch, int32_t num_features, const viekf_params* 
       return fail(VIEKF_ERR_HIP, std::string("hipMalloc failed: ") + hipGetErrorString(e_)); \
     }                                                                            \
   } while (0)
-  ALLOC(b->d_x, sizeof(double) * (size_t)batch * b->nxs);
-  ALLOC(b->d_P, sizeof(double) * (size_t)batch * b->n * b->ld);
+  ALLOC(b->home_x, sizeof(double) * (size_t)batch * b->nxs);
+  ALLOC(b->home_P, sizeof(double) * (size_t)batch * b->n * b->ld);
+  point_live(b);
   ALLOC(b->d_Qx, sizeof(double) * (size_t)b->n);
   ALLOC(b->d_lambda, sizeof(double) * (size_t)b->n);
   ALLOC(b->d_Pdiag, sizeof(double) * (size_t)b->n);
@@ -186,7 +187,7 @@ int viekf_batch_destroy(viekf_batch* b) {
   if (b->stream) (void)hipStreamSynchronize(b->stream);
   if (b->d_smap) (void)hipFree(b->d_smap);
   if (b->d_zero) (void)hipFree(b->d_zero);
-  void* ptrs[] = {b->home_x ? b->home_x : b->d_x, b->home_P ? b->home_P : b->d_P, b->d_Qx, b->d_lambda, b->d_Pdiag, b->d_x0, b->d_ws, b->d_len, b->d_flags, b->d_stage, b->d_dp, b->h_x, b->h_P, b->h_len, b->d_active, b->d_ringslot, b->d_resmap, b->d_diag_ws};
+  void* ptrs[] = {b->home_x, b->home_P, b->d_Qx, b->d_lambda, b->d_Pdiag, b->d_x0, b->d_ws, b->d_len, b->d_flags, b->d_stage, b->d_dp, b->h_x, b->h_P, b->h_len, b->d_active, b->d_ringslot, b->d_resmap, b->d_diag_ws};
   for (void* q : ptrs)
     if (q) (void)hipFree(q);
   if (b->h_pin) (void)hipHostFree(b->h_pin);
@@ -201,7 +202,7 @@ int viekf_batch_reset(viekf_batch* b) {
   StreamArgs a = make_args(b);
   hipLaunchKernelGGL(k_reset, dim3(b->B), dim3(256), 0, b->stream, a, b->d_x0, b->d_Pdiag);
   HIP_TRY(hipGetLastError());
-  set_level(b, 0);   // (k_reset writes all of P)
+  b->book.wrote_live(PForm::Full);   // (k_reset writes all of P)
   HIP_TRY(hipStreamSynchronize(b->stream));
   return VIEKF_OK;
 }
@@ -232,7 +233,7 @@ int viekf_batch_describe(const viekf_batch* b, char* out, int32_t cap) {
              r.max_lds_kb <= 40 ? "4 workgroups" : (r.max_lds_kb <= 80 ? "2 workgroups" : "1 workgroup"), b->res_lds / 1024);
     const size_t len = strlen(buf);
     snprintf(buf + len, sizeof buf - len, "; P %s between launches",
-             (b->tune_packed_p && packed_fits(b) && !b->per_filter) ? "packed" : "canonical");
+             keeps_packed(b) ? "packed" : "canonical");
   } else {
     const int bg = blocked_group(b, nullptr);
     if (bg > 0)
@@ -297,7 +298,7 @@ int viekf_batch_set_tuning(viekf_batch* b, int32_t key, int32_t value) {
       b->tune_res_inst = value;
       break;
     case VIEKF_TUNE_PACKED_P:
-      if (int rc = ensure_full_P(b, 2)) return rc;   // (ring slots keep their form: it is recorded per slot)
+      if (int rc = require_P(b, PForm::Lower)) return rc;   // (ring slots keep their form: it is recorded per slot)
       b->tune_packed_p = value != 0;
       return VIEKF_OK;
     case VIEKF_TUNE_UNIT_LAMBDA:
@@ -319,7 +320,7 @@ int viekf_batch_set_tuning(viekf_batch* b, int32_t key, int32_t value) {
     case VIEKF_TUNE_STREAM_MFMA:
       if (value < 0 || value > 2) return fail(VIEKF_ERR_INVALID, "stream MFMA: 0 off, 1 on, 2 on with r02's scratch-staged propagate");
       b->tune_stream_mfma = value;
-      if (!b->tune_stream_mfma) { if (int rc = ensure_full_P(b)) return rc; }   // (the plain kernels read all of P)
+      if (!b->tune_stream_mfma) { if (int rc = require_P(b, PForm::Full)) return rc; }   // (the plain kernels read all of P)
       return VIEKF_OK;
     default:
       return fail(VIEKF_ERR_INVALID, "unknown tuning key");
@@ -339,8 +340,8 @@ int viekf_batch_get_state(viekf_batch* b, double* x, double* P, int32_t* len_fea
   HIP_TRY(hipSetDevice(b->device));
   const hipMemcpyKind kind = where == VIEKF_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
   const double *sx = b->d_x, *sP = b->d_P;
-  if (P) if (int rc = ensure_full_P(b)) return rc;
-  if (b->per_filter && (x || P)) {   // every filter's live slot -> the batch's own buffers, then out as usual
+  if (P) if (int rc = require_P(b, PForm::Full)) return rc;
+  if (b->book.per_filter() && (x || P)) {   // every filter's live slot -> the batch's own buffers, then out as usual
     if (int rc = gather_scatter_home(b, 1)) return rc;
     sx = b->home_x; sP = b->home_P;
   }
@@ -365,8 +366,8 @@ int viekf_batch_set_state(viekf_batch* b, const double* x, const double* P, cons
       if (len_features[i] < 0 || len_features[i] > b->N)
         return fail(VIEKF_ERR_INVALID, "len_features out of range");
   double *tx = b->d_x, *tP = b->d_P;
-  if (b->per_filter && (x || P)) {   // through the batch's own buffers: what is not given keeps its value
-    if (int rc = ensure_full_P(b)) return rc;
+  if (b->book.per_filter() && (x || P)) {   // through the batch's own buffers: what is not given keeps its value
+    if (int rc = require_P(b, PForm::Full)) return rc;
     if (int rc = gather_scatter_home(b, 1)) return rc;
     tx = b->home_x; tP = b->home_P;
   }
@@ -376,7 +377,7 @@ int viekf_batch_set_state(viekf_batch* b, const double* x, const double* P, cons
   if (P)
     HIP_TRY(hipMemcpy2DAsync(tP, sizeof(double) * b->ld, P, sizeof(double) * b->n, sizeof(double) * b->n,
                              (size_t)b->B * b->n, kind, b->stream));
-  if (b->per_filter && (x || P))
+  if (b->book.per_filter() && (x || P))
     if (int rc = gather_scatter_home(b, 0)) return rc;
   if (len_features) HIP_TRY(hipMemcpyAsync(b->d_len, len_features, sizeof(int32_t) * b->B, kind, b->stream));
   if (P) {
@@ -386,7 +387,7 @@ int viekf_batch_set_state(viekf_batch* b, const double* x, const double* P, cons
     const long tot = (long)b->n * b->n;
     hipLaunchKernelGGL(k_symmetrize, dim3((unsigned)((tot + 255) / 256), b->B), dim3(256), 0, b->stream, a);
     HIP_TRY(hipGetLastError());
-    set_level(b, 0);   // (all of P was given)
+    b->book.wrote_live(PForm::Full);   // (all of P was given)
   }
   if (where == VIEKF_HOST) HIP_TRY(hipStreamSynchronize(b->stream));
   return VIEKF_OK;
@@ -422,7 +423,7 @@ int viekf_batch_init_feature(viekf_batch* b, const double* pix, const double* de
   if (int rc = check_batch(b)) return rc;
   if (!pix) return fail(VIEKF_ERR_INVALID, "pix must not be null");
   HIP_TRY(hipSetDevice(b->device));
-  if (int rc = need_canonical_P(b)) return rc;   // (writes the new feature's rows and columns in place)
+  if (int rc = require_P(b, PForm::Lower)) return rc;   // (writes the new feature's rows and columns in place)
   const double *d_pix = nullptr, *d_depth = nullptr;
   const uint8_t* d_mask = nullptr;
   int* d_ok = nullptr;
@@ -480,7 +481,7 @@ int viekf_debug_read_ws(viekf_batch* b, void* out, int count) {
 
 int viekf_batch_keep_features(viekf_batch* b, const uint8_t* keep, int32_t* new_len, viekf_mem where) {
   if (int rc = check_batch(b)) return rc;
-  if (int rc = need_full_P(b)) return rc;
+  if (int rc = require_P(b, PForm::Full)) return rc;
   if (!keep) return fail(VIEKF_ERR_INVALID, "keep must not be null");
   HIP_TRY(hipSetDevice(b->device));
   const size_t BN = (size_t)b->B * b->N;
@@ -497,7 +498,7 @@ int viekf_batch_keep_features(viekf_batch* b, const uint8_t* keep, int32_t* new_
 
 int viekf_batch_keyframe_reset(viekf_batch* b, const uint8_t* mask, double* edge, viekf_mem where) {
   if (int rc = check_batch(b)) return rc;
-  if (int rc = need_full_P(b)) return rc;
+  if (int rc = require_P(b, PForm::Full)) return rc;
   HIP_TRY(hipSetDevice(b->device));
   const uint8_t* d_mask = nullptr;
   double* d_edge = nullptr;
@@ -632,7 +633,7 @@ int viekf_batch_get_cov_diag(viekf_batch* b, double* diag, viekf_mem where) {
   if (int rc = check_batch(b)) return rc;
   if (!diag) return fail(VIEKF_ERR_INVALID, "diag is null");
   HIP_TRY(hipSetDevice(b->device));
-  if (int rc = need_canonical_P(b)) return rc;
+  if (int rc = require_P(b, PForm::Lower)) return rc;
   double* d_o = nullptr;
   Staged st(b, where);
   if (int rc = st.begin(out(diag, (size_t)b->B * b->n, &d_o))) return rc;
@@ -646,7 +647,7 @@ int viekf_batch_get_cov_block(viekf_batch* b, int32_t row0, int32_t col0, int32_
                               viekf_mem where) {
   if (int rc = check_batch(b)) return rc;
   if (!block) return fail(VIEKF_ERR_INVALID, "out is null");
-  if (int rc = need_full_P(b)) return rc;
+  if (int rc = require_P(b, PForm::Full)) return rc;
   if (row0 < 0 || col0 < 0 || nrows < 1 || ncols < 1 || row0 + nrows > b->n || col0 + ncols > b->n)
     return fail(VIEKF_ERR_INVALID, "block outside the covariance");
   HIP_TRY(hipSetDevice(b->device));
@@ -664,18 +665,16 @@ int viekf_batch_history_resize(viekf_batch* b, int32_t depth) {
   if (depth < 0 || depth > 4096) return fail(VIEKF_ERR_INVALID, "0 <= depth <= 4096");
   HIP_TRY(hipSetDevice(b->device));
   HIP_TRY(hipStreamSynchronize(b->stream));
-  if (b->per_filter) {       // every filter's live slot goes home
+  if (b->book.per_filter()) {       // every filter's live slot goes home
     if (int rc = gather_scatter_home(b, 1)) return rc;
     HIP_TRY(hipStreamSynchronize(b->stream));
-    b->d_x = b->home_x; b->d_P = b->home_P; b->per_filter = false;
   }
-  if (b->live_slot >= 0) {   // the live state lives in the ring: bring it home first
+  if (b->book.live_slot() >= 0) {   // the live state lives in the ring: bring it home first, as it stands
     HIP_TRY(hipMemcpy(b->home_x, b->d_x, hist_nx(b), hipMemcpyDeviceToDevice));
     HIP_TRY(hipMemcpy(b->home_P, b->d_P, hist_nP(b), hipMemcpyDeviceToDevice));
-    b->d_x = b->home_x; b->d_P = b->home_P; b->live_slot = -1;
-    b->home_packed = b->upper_stale == 3;   // (copied as it stands)
   }
-  b->slot_packed.clear();
+  b->book.resized(0);
+  point_live(b);
   if (b->h_x) { HIP_TRY(hipFree(b->h_x)); b->h_x = nullptr; }
   if (b->h_P) { HIP_TRY(hipFree(b->h_P)); b->h_P = nullptr; }
   if (b->h_len) { HIP_TRY(hipFree(b->h_len)); b->h_len = nullptr; }
@@ -685,33 +684,25 @@ int viekf_batch_history_resize(viekf_batch* b, int32_t depth) {
   HIP_TRY(hipMalloc(&b->h_P, sizeof(double) * (size_t)depth * b->B * b->n * b->ld));
   HIP_TRY(hipMalloc(&b->h_len, sizeof(int) * (size_t)depth * b->B));
   b->hist_depth = depth;
-  b->slot_packed.assign((size_t)depth, 0);
+  b->book.resized(depth);
   return VIEKF_OK;
 }
 
 static int history_copy(viekf_batch* b, int32_t slot, bool save) {
   if (int rc = check_batch(b)) return rc;
   if (slot < 0 || slot >= b->hist_depth) return fail(VIEKF_ERR_INVALID, "snapshot slot out of range (viekf_batch_history_resize first)");
-  if (b->per_filter) return fail(VIEKF_ERR_INVALID, "whole-batch ring copies under per-filter live slots (viekf_batch_select_filters)");
+  if (b->book.per_filter()) return fail(VIEKF_ERR_INVALID, "whole-batch ring copies under per-filter live slots (viekf_batch_select_filters)");
   // (the covariance is copied as it stands, packed or not: the form travels with it)
-  if (save) b->slot_packed[(size_t)slot] = b->upper_stale == 3; else mark_live_from(b, b->slot_packed[(size_t)slot] != 0);
+  if (save) b->book.saved_to(slot); else b->book.restored_from(slot);
   HIP_TRY(hipSetDevice(b->device));
-  const size_t nl = sizeof(int) * (size_t)b->B;
-  char* hl = reinterpret_cast<char*>(b->h_len) + nl * slot;
-  const bool same = slot == b->live_slot;   // the live state already IS this slot: only the feature counts move
-  if (save) {
-    if (!same) {
-      HIP_TRY(hipMemcpyAsync(slot_x(b, slot), b->d_x, hist_nx(b), hipMemcpyDeviceToDevice, b->stream));
-      HIP_TRY(hipMemcpyAsync(slot_P(b, slot), b->d_P, hist_nP(b), hipMemcpyDeviceToDevice, b->stream));
-    }
-    HIP_TRY(hipMemcpyAsync(hl, b->d_len, nl, hipMemcpyDeviceToDevice, b->stream));
-  } else {
-    if (!same) {
-      HIP_TRY(hipMemcpyAsync(b->d_x, slot_x(b, slot), hist_nx(b), hipMemcpyDeviceToDevice, b->stream));
-      HIP_TRY(hipMemcpyAsync(b->d_P, slot_P(b, slot), hist_nP(b), hipMemcpyDeviceToDevice, b->stream));
-    }
-    HIP_TRY(hipMemcpyAsync(b->d_len, hl, nl, hipMemcpyDeviceToDevice, b->stream));
+  struct State { double *x, *P; int* len; };
+  const State live = {b->d_x, b->d_P, b->d_len}, ring = {slot_x(b, slot), slot_P(b, slot), b->h_len + (size_t)b->B * slot};
+  const State &src = save ? live : ring, &dst = save ? ring : live;
+  if (slot != b->book.live_slot()) {   // (the live state already IS this slot: only the feature counts move)
+    HIP_TRY(hipMemcpyAsync(dst.x, src.x, hist_nx(b), hipMemcpyDeviceToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(dst.P, src.P, hist_nP(b), hipMemcpyDeviceToDevice, b->stream));
   }
+  HIP_TRY(hipMemcpyAsync(dst.len, src.len, sizeof(int) * (size_t)b->B, hipMemcpyDeviceToDevice, b->stream));
   return VIEKF_OK;
 }
 int viekf_batch_snapshot(viekf_batch* b, int32_t slot) { return history_copy(b, slot, true); }
@@ -741,14 +732,14 @@ static int ring_filters(viekf_batch* b, const int32_t* slot, viekf_mem where, in
   if (int rc = check_batch(b)) return rc;
   if (!slot) return fail(VIEKF_ERR_INVALID, "slot is null");
   if (b->hist_depth <= 0) return fail(VIEKF_ERR_INVALID, "no history ring (viekf_batch_history_resize first)");
-  if (b->live_slot >= 0) return fail(VIEKF_ERR_INVALID, "per-filter ring copies need the live state in the batch's own buffers (viekf_batch_select(-1))");
+  if (b->book.live_slot() >= 0) return fail(VIEKF_ERR_INVALID, "per-filter ring copies need the live state in the batch's own buffers (viekf_batch_select(-1))");
   HIP_TRY(hipSetDevice(b->device));
   // (host slots are validated here; device slots by the kernel, which skips an out-of-range one and raises VIEKF_FLAG_INTERNAL)
   if (where == VIEKF_HOST)
     for (int i = 0; i < b->B; i++)
       if (slot[i] >= b->hist_depth) return fail(VIEKF_ERR_INVALID, "ring slot out of range");
   if (int rc = canonicalize_all(b)) return rc;   // (single filters move between buffers: no buffer may end up of mixed form)
-  if (!to_ring) mark_restored_stale(b);
+  if (!to_ring) b->book.filters_moved();
   const int* d_slot = nullptr;
   Staged st(b, where);
   if (where == VIEKF_HOST && !b->async_host) {   // (a buffer of the batch's own, not the staging region)
@@ -769,12 +760,9 @@ int viekf_batch_restore_filters(viekf_batch* b, const int32_t* slot, viekf_mem w
 int viekf_batch_select(viekf_batch* b, int32_t slot) {
   if (int rc = check_batch(b)) return rc;
   if (slot < -1 || slot >= b->hist_depth) return fail(VIEKF_ERR_INVALID, "ring slot out of range (viekf_batch_history_resize first)");
-  if (b->per_filter) return fail(VIEKF_ERR_INVALID, "viekf_batch_select under per-filter live slots (viekf_batch_select_filters)");
-  if (!b->home_x) { b->home_x = b->d_x; b->home_P = b->d_P; }
-  b->live_slot = slot;
-  b->d_x = slot < 0 ? b->home_x : slot_x(b, slot);
-  b->d_P = slot < 0 ? b->home_P : slot_P(b, slot);
-  mark_live_from(b, *live_form(b) != 0);   // (the buffer's own form; canonical: as stale as anything this batch produced)
+  if (b->book.per_filter()) return fail(VIEKF_ERR_INVALID, "viekf_batch_select under per-filter live slots (viekf_batch_select_filters)");
+  b->book.select(slot);
+  point_live(b);
   return VIEKF_OK;
 }
 
@@ -782,8 +770,8 @@ int viekf_batch_propagate_to(viekf_batch* b, const double* u, const double* dt, 
   if (int rc = check_batch(b)) return rc;
   if (!u || !dt) return fail(VIEKF_ERR_INVALID, "u and dt must not be null");
   if (dst_slot < 0 || dst_slot >= b->hist_depth) return fail(VIEKF_ERR_INVALID, "ring slot out of range (viekf_batch_history_resize first)");
-  if (b->per_filter) return fail(VIEKF_ERR_INVALID, "viekf_batch_propagate_to under per-filter live slots (viekf_batch_propagate_filters_to)");
-  if (dst_slot == b->live_slot) return viekf_batch_propagate(b, u, dt, where);
+  if (b->book.per_filter()) return fail(VIEKF_ERR_INVALID, "viekf_batch_propagate_to under per-filter live slots (viekf_batch_propagate_filters_to)");
+  if (dst_slot == b->book.live_slot()) return viekf_batch_propagate(b, u, dt, where);
   // (a filter outside a participation mask would have nothing written into the destination slot, which then becomes the live
   //  state: the zero-copy ring is for filters that advance together)
   if (b->active_on) return fail(VIEKF_ERR_INVALID, "viekf_batch_propagate_to under a participation mask (viekf_batch_set_active(NULL) first)");
@@ -798,7 +786,7 @@ int viekf_batch_propagate_to(viekf_batch* b, const double* u, const double* dt, 
   } else {                 // streaming family works in place: copy, then propagate the copy
     HIP_TRY(hipMemcpyAsync(slot_x(b, dst_slot), b->d_x, hist_nx(b), hipMemcpyDeviceToDevice, b->stream));
     HIP_TRY(hipMemcpyAsync(slot_P(b, dst_slot), b->d_P, hist_nP(b), hipMemcpyDeviceToDevice, b->stream));
-    b->slot_packed[(size_t)dst_slot] = b->upper_stale == 3;
+    b->book.saved_to(dst_slot);
     if (int rc = viekf_batch_select(b, dst_slot)) return rc;
     if (int rc = launch_propagate(b, d_u, d_dt)) return rc;
   }
@@ -810,10 +798,10 @@ int viekf_batch_propagate_n_to(viekf_batch* b, int32_t K, const double* u, const
   if (int rc = check_batch(b)) return rc;
   if (!u || !dt || !dst_slots) return fail(VIEKF_ERR_INVALID, "u, dt and dst_slots must not be null");
   if (K < 1 || K > 64) return fail(VIEKF_ERR_INVALID, "1 <= K <= 64 propagates per call");
-  if (b->per_filter) return fail(VIEKF_ERR_INVALID, "viekf_batch_propagate_n_to under per-filter live slots");
+  if (b->book.per_filter()) return fail(VIEKF_ERR_INVALID, "viekf_batch_propagate_n_to under per-filter live slots");
   for (int k = 0; k < K; k++) {
     if (dst_slots[k] < 0 || dst_slots[k] >= b->hist_depth) return fail(VIEKF_ERR_INVALID, "ring slot out of range (viekf_batch_history_resize first)");
-    if (dst_slots[k] == b->live_slot) return fail(VIEKF_ERR_INVALID, "a destination slot is the live slot");
+    if (dst_slots[k] == b->book.live_slot()) return fail(VIEKF_ERR_INVALID, "a destination slot is the live slot");
     for (int j = 0; j < k; j++)
       if (dst_slots[j] == dst_slots[k]) return fail(VIEKF_ERR_INVALID, "destination slots must differ");
   }
@@ -840,19 +828,18 @@ int viekf_batch_select_filters(viekf_batch* b, const int32_t* slot) {
   if (int rc = check_batch(b)) return rc;
   if (!slot) return fail(VIEKF_ERR_INVALID, "slot is null");
   if (b->hist_depth <= 0) return fail(VIEKF_ERR_INVALID, "no history ring (viekf_batch_history_resize first)");
-  if (b->live_slot >= 0) return fail(VIEKF_ERR_INVALID, "per-filter live slots need the live state in the batch's own buffers (viekf_batch_select(-1))");
+  if (b->book.live_slot() >= 0) return fail(VIEKF_ERR_INVALID, "per-filter live slots need the live state in the batch's own buffers (viekf_batch_select(-1))");
   for (int i = 0; i < b->B; i++) {
     if (slot[i] >= b->hist_depth) return fail(VIEKF_ERR_INVALID, "ring slot out of range");
-    if (slot[i] < 0 && !b->per_filter) return fail(VIEKF_ERR_INVALID, "the first call has to name a slot for every filter");
+    if (slot[i] < 0 && !b->book.per_filter()) return fail(VIEKF_ERR_INVALID, "the first call has to name a slot for every filter");
   }
   HIP_TRY(hipSetDevice(b->device));
   if (int rc = canonicalize_all(b)) return rc;   // (per-filter live slots keep today's canonical path: every buffer first)
-  if (!b->per_filter) {
+  if (!b->book.per_filter()) {
     if (!b->d_smap) HIP_TRY(hipMalloc(&b->d_smap, sizeof(int) * (size_t)b->B));
-    if (!b->home_x) { b->home_x = b->d_x; b->home_P = b->d_P; }
     b->live_slots.assign((size_t)b->B, 0);
-    b->per_filter = true;
-    b->d_x = b->h_x; b->d_P = b->h_P;
+    b->book.enter_per_filter();
+    point_live(b);
   }
   for (int i = 0; i < b->B; i++)
     if (slot[i] >= 0) b->live_slots[(size_t)i] = slot[i];
@@ -863,14 +850,56 @@ int viekf_batch_select_filters(viekf_batch* b, const int32_t* slot) {
   hipLaunchKernelGGL(k_set_smap, dim3((unsigned)((b->B + 255) / 256)), dim3(256), 0, b->stream, b->d_smap, d_slot, b->B);
   HIP_TRY(hipGetLastError());
   if (int rc = st.finish(true)) return rc;
-  mark_restored_stale(b);
+  b->book.filters_moved();
   return VIEKF_OK;
+}
+
+// The one masked launch behind both per-filter propagate entry points (which have checked every argument): filter i with
+// dst_slot[i] >= 0 -- and k_count[i] > 0 where counts are given -- goes from its live slot into dst_slot[i], by k_count[i]
+// propagates (one without counts; counts are for the fused family only); every other filter is outside the launch's own mask.
+// u / dt hold Kstaged propagates per filter, kmax is the most any filter takes.
+static int propagate_filters_masked(viekf_batch* b, const double* u, const double* dt, int Kstaged, int kmax, const int32_t* k_count,
+                                    const int32_t* dst_slot, viekf_mem where) {
+  const size_t B = (size_t)b->B;
+  // the participation mask and the destination map of THIS launch, through the pinned staging like the other per-call arguments
+  std::vector<unsigned char> act(B);
+  std::vector<int32_t> omap(B), kc(k_count ? B : 0);
+  for (size_t i = 0; i < B; i++) {
+    const bool on = dst_slot[i] >= 0 && (!k_count || k_count[i] > 0);
+    act[i] = on ? 1 : 0;
+    omap[i] = (on ? dst_slot[i] : b->live_slots[i]) * b->B + (int32_t)i;
+    if (k_count) kc[i] = on ? k_count[i] : 1;   // (a filter outside the mask never reads it)
+  }
+  const bool in_place = !use_resident(b);   // (the HBM-path family: it needs the destination slots themselves instead of counts)
+  const double *d_u = nullptr, *d_dt = nullptr;
+  const unsigned char* d_act = nullptr;
+  const int32_t *d_omap = nullptr, *d_extra = nullptr;
+  Staged st(b, where);
+  if (int rc = st.begin(in(u, 6 * B * (size_t)Kstaged, &d_u), in(dt, B * (size_t)Kstaged, &d_dt), in_host(act.data(), B, &d_act),
+                        in_host(omap.data(), B, &d_omap), in_host(in_place ? dst_slot : (k_count ? kc.data() : nullptr), B, &d_extra)))
+    return rc;
+  if (!in_place) {   // the fused kernel loads filter b from its live slot and stores it into dst_slot[b]: no copy at all
+    if (int rc = launch_resident(b, true, d_u, d_dt, nullptr, nullptr, 0, nullptr, 0, nullptr, -1, kmax, d_omap, k_count ? d_extra : nullptr, d_act))
+      return rc;
+  } else {           // the HBM-path family works in place: copy slot -> slot, then propagate the copy
+    StreamArgs a = make_args(b, d_act);
+    hipLaunchKernelGGL(k_ring_copy, dim3(b->B), dim3(256), 0, b->stream, a, b->h_x, b->h_P, d_extra, 1, b->hist_depth);
+    if (hipGetLastError() != hipSuccess) return fail(VIEKF_ERR_HIP, "k_ring_copy launch failed");
+  }
+  for (size_t i = 0; i < B; i++)   // (the fused kernel moves the device's map entries itself)
+    if (act[i]) b->live_slots[i] = dst_slot[i];
+  if (in_place) {
+    hipLaunchKernelGGL(k_set_smap, dim3((unsigned)((b->B + 255) / 256)), dim3(256), 0, b->stream, b->d_smap, d_extra, b->B);
+    if (hipGetLastError() != hipSuccess) return fail(VIEKF_ERR_HIP, "k_set_smap launch failed");
+    if (int rc = launch_propagate(b, d_u, d_dt, d_act)) return rc;
+  }
+  return st.finish(true);
 }
 
 int viekf_batch_propagate_filters_to(viekf_batch* b, const double* u, const double* dt, const int32_t* dst_slot, viekf_mem where) {
   if (int rc = check_batch(b)) return rc;
   if (!u || !dt || !dst_slot) return fail(VIEKF_ERR_INVALID, "u, dt and dst_slot must not be null");
-  if (!b->per_filter) return fail(VIEKF_ERR_INVALID, "viekf_batch_select_filters first");
+  if (!b->book.per_filter()) return fail(VIEKF_ERR_INVALID, "viekf_batch_select_filters first");
   // (the launch runs under a mask of its own, dst_slot[b] >= 0: a caller's mask would be ignored and a filter it masked out
   //  stepped anyway -- refused like viekf_batch_propagate_to)
   if (b->active_on)
@@ -883,45 +912,7 @@ int viekf_batch_propagate_filters_to(viekf_batch* b, const double* u, const doub
   }
   if (!any) return VIEKF_OK;
   HIP_TRY(hipSetDevice(b->device));
-  const size_t B = (size_t)b->B;
-  // the participation mask and the destination map of THIS launch, through the pinned staging like the other per-call arguments
-  std::vector<unsigned char> act(B);
-  std::vector<int32_t> omap(B);
-  for (size_t i = 0; i < B; i++) {
-    act[i] = dst_slot[i] >= 0 ? 1 : 0;
-    omap[i] = (dst_slot[i] >= 0 ? dst_slot[i] : b->live_slots[i]) * b->B + (int32_t)i;
-  }
-  const double *d_u = nullptr, *d_dt = nullptr;
-  const unsigned char* d_act = nullptr;
-  const int32_t *d_omap = nullptr, *d_dst = nullptr;
-  const bool in_place = !use_resident(b);   // (the HBM-path family: it needs the destination slots themselves as well)
-  Staged st(b, where);
-  if (int rc = st.begin(in(u, 6 * B, &d_u), in(dt, B, &d_dt), in_host(act.data(), B, &d_act), in_host(omap.data(), B, &d_omap),
-                        in_host(in_place ? dst_slot : nullptr, B, &d_dst)))
-    return rc;
-  const bool saved_on = b->active_on;
-  unsigned char* saved_mask = b->d_active;
-  b->active_on = true; b->d_active = const_cast<unsigned char*>(d_act);
-  int rc = VIEKF_OK;
-  if (!in_place) {           // the fused kernel loads filter b from its live slot and stores it into dst_slot[b]: no copy at all
-    rc = launch_resident(b, true, d_u, d_dt, nullptr, nullptr, 0, nullptr, 0, nullptr, -1, 1, d_omap);
-    for (size_t i = 0; i < B && rc == VIEKF_OK; i++)     // (the kernel moves the device's map entries itself)
-      if (dst_slot[i] >= 0) b->live_slots[i] = dst_slot[i];
-  } else {                   // the HBM-path family works in place: copy slot -> slot, then propagate the copy
-    StreamArgs a = make_args(b);
-    hipLaunchKernelGGL(k_ring_copy, dim3(b->B), dim3(256), 0, b->stream, a, b->h_x, b->h_P, d_dst, 1, b->hist_depth);
-    if (hipGetLastError() != hipSuccess) rc = fail(VIEKF_ERR_HIP, "k_ring_copy launch failed");
-    if (rc == VIEKF_OK) {
-      for (size_t i = 0; i < B; i++)
-        if (dst_slot[i] >= 0) b->live_slots[i] = dst_slot[i];
-      hipLaunchKernelGGL(k_set_smap, dim3((unsigned)((b->B + 255) / 256)), dim3(256), 0, b->stream, b->d_smap, d_dst, b->B);
-      if (hipGetLastError() != hipSuccess) rc = fail(VIEKF_ERR_HIP, "k_set_smap launch failed");
-    }
-    if (rc == VIEKF_OK) rc = launch_propagate(b, d_u, d_dt);
-  }
-  b->active_on = saved_on; b->d_active = saved_mask;
-  if (rc) return rc;
-  return st.finish(true);
+  return propagate_filters_masked(b, u, dt, 1, 1, nullptr, dst_slot, where);
 }
 
 int viekf_batch_propagate_n_filters_to(viekf_batch* b, int32_t Kmax, const double* u, const double* dt, const int32_t* k_count,
@@ -929,7 +920,7 @@ int viekf_batch_propagate_n_filters_to(viekf_batch* b, int32_t Kmax, const doubl
   if (int rc = check_batch(b)) return rc;
   if (!u || !dt || !k_count || !dst_slot) return fail(VIEKF_ERR_INVALID, "u, dt, k_count and dst_slot must not be null");
   if (Kmax < 1 || Kmax > 64) return fail(VIEKF_ERR_INVALID, "1 <= Kmax <= 64 propagates per call");
-  if (!b->per_filter) return fail(VIEKF_ERR_INVALID, "viekf_batch_select_filters first");
+  if (!b->book.per_filter()) return fail(VIEKF_ERR_INVALID, "viekf_batch_select_filters first");
   if (b->active_on)   // (the call runs under a mask of its own, like viekf_batch_propagate_filters_to)
     return fail(VIEKF_ERR_INVALID, "viekf_batch_propagate_n_filters_to under a participation mask (viekf_batch_set_active(NULL) first; k_count 0 or dst_slot < 0 skips a filter)");
   const size_t B = (size_t)b->B;
@@ -948,34 +939,9 @@ int viekf_batch_propagate_n_filters_to(viekf_batch* b, int32_t Kmax, const doubl
   if (intermediates_written) *intermediates_written = 0;
   if (kmax == 0) return VIEKF_OK;
   HIP_TRY(hipSetDevice(b->device));
-  if (kmax >= 2 && use_resident(b) && !use_tiles(b)) {
-    // ONE launch of the fused kernel's multi-propagate instance: filter b is loaded from its live slot, P stays on chip through its
-    // own k_count[b] propagates and is stored into dst_slot[b] only
-    std::vector<unsigned char> act(B);
-    std::vector<int32_t> omap(B), kc(B);
-    for (size_t i = 0; i < B; i++) {
-      const bool on = k_count[i] > 0 && dst_slot[i] >= 0;
-      act[i] = on ? 1 : 0;
-      omap[i] = (on ? dst_slot[i] : b->live_slots[i]) * b->B + (int32_t)i;
-      kc[i] = on ? k_count[i] : 1;   // (a filter outside the mask never reads it)
-    }
-    const double *d_u = nullptr, *d_dt = nullptr;
-    const unsigned char* d_act = nullptr;
-    const int32_t *d_omap = nullptr, *d_kc = nullptr;
-    Staged st(b, where);
-    if (int rc = st.begin(in(u, 6 * B * (size_t)Kmax, &d_u), in(dt, B * (size_t)Kmax, &d_dt), in_host(act.data(), B, &d_act),
-                          in_host(omap.data(), B, &d_omap), in_host(kc.data(), B, &d_kc)))
-      return rc;
-    const bool saved_on = b->active_on;
-    unsigned char* saved_mask = b->d_active;
-    b->active_on = true; b->d_active = const_cast<unsigned char*>(d_act);
-    const int rc = launch_resident(b, true, d_u, d_dt, nullptr, nullptr, 0, nullptr, 0, nullptr, -1, kmax, d_omap, d_kc);
-    b->active_on = saved_on; b->d_active = saved_mask;
-    if (rc) return rc;
-    for (size_t i = 0; i < B; i++)   // (the launch is issued: the kernel moves the device's map entries itself)
-      if (act[i]) b->live_slots[i] = dst_slot[i];
-    return st.finish(true);
-  }
+  // ONE launch of the fused kernel's multi-propagate instance: filter b is loaded from its live slot, P stays on chip through its
+  // own k_count[b] propagates and is stored into dst_slot[b] only
+  if (kmax >= 2 && use_resident(b) && !use_tiles(b)) return propagate_filters_masked(b, u, dt, Kmax, kmax, k_count, dst_slot, where);
   // Step by step (the HBM-path family, the tile family, one propagate per filter): step k of filter b goes into dst_slot[b] or
   // into its scratch slot -- the slot after dst_slot[b] in ring order that is not its live slot -- by turns, the last one into
   // dst_slot[b].  (viekf_batch_propagate_filters_to moves the host's live-slot mirror after each step it has issued.)
@@ -1000,7 +966,7 @@ int viekf_batch_propagate_n_filters_to(viekf_batch* b, int32_t Kmax, const doubl
 int viekf_batch_update(viekf_batch* b, int32_t type, const double* z, int32_t zdim, const double* R, int32_t rdim,
                        int32_t r_mode, const int32_t* slot, const uint8_t* active, int32_t* result, viekf_mem where) {
   if (int rc = check_batch(b)) return rc;
-  if (int rc = need_full_P(b)) return rc;
+  if (int rc = require_P(b, PForm::Full)) return rc;
   if (!z || !R) return fail(VIEKF_ERR_INVALID, "z and R must not be null");
   if (type < 0 || type >= VIEKF_TOTAL_MEAS || type == VIEKF_PIXEL_VEL)
     return fail(VIEKF_ERR_UNSUPPORTED, "measurement type not supported (PIXEL_VEL is an empty TODO in the reference)");
@@ -1048,7 +1014,7 @@ int viekf_diag_consistency(viekf_batch* b, const double* x_true, double* logdet,
   if (!logdet && !nees && !whitened && !info) return fail(VIEKF_ERR_INVALID, "at least one output must not be null");
   if (!x_true && (nees || whitened)) return fail(VIEKF_ERR_INVALID, "nees and whitened need x_true");
   HIP_TRY(hipSetDevice(b->device));
-  if (int rc = need_canonical_P(b)) return rc;
+  if (int rc = require_P(b, PForm::Lower)) return rc;
   const size_t B = (size_t)b->B;
   const double* d_xt = nullptr;
   double *d_ld = nullptr, *d_ne = nullptr, *d_wh = nullptr;
@@ -1098,7 +1064,7 @@ int viekf_diag_innovation(viekf_batch* b, int32_t type, int32_t M, const double*
   if (needs_slot && !slot) return fail(VIEKF_ERR_INVALID, "slot must not be null for feature measurements");
   if (!needs_slot && (M != 1 || slot)) return fail(VIEKF_ERR_INVALID, "this measurement model takes M == 1 and no slot");
   HIP_TRY(hipSetDevice(b->device));
-  if (int rc = need_canonical_P(b)) return rc;
+  if (int rc = require_P(b, PForm::Lower)) return rc;
   const size_t BM = (size_t)b->B * (size_t)M, rr = (size_t)rdim * rdim;
   const double *d_z = nullptr, *d_R = nullptr;
   const int32_t* d_slot = nullptr;

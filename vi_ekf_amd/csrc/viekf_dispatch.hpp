@@ -52,16 +52,16 @@ size_t lds_propagate(const viekf_batch* b) {
 size_t lds_update(const viekf_batch* b) { return sizeof(double) * (size_t)(b->nxs + 5 * b->n + 32); }
 
 // A grouped update (k_update_feat_blocked) keeps only the lower triangle of P current; the matrix-core propagate reads only
-// that and rewrites all of P; a fused launch may leave P packed.  Everything else reads P whole (or at least canonical): see
-// ensure_full_P below the kernel tables.
-int ensure_full_P(viekf_batch* b, int tolerate = 0);
+// that and rewrites all of P; a fused launch may leave P packed.  Every reader says which form it can take: require_P, below
+// the kernel tables.
+int require_P(viekf_batch* b, PForm at_most);
 
 // (VIEKF_TUNE_STREAM_MFMA = 0 keeps the kernels without matrix-core passes: experiments)
 bool stream_mfma_ok(const viekf_batch* b) { return b->tune_stream_mfma != 0; }
 
-int launch_propagate(viekf_batch* b, const double* d_u, const double* d_dt) {
-  if (int rc = ensure_full_P(b, stream_mfma_ok(b) ? 2 : 0)) return rc;
-  StreamArgs a = make_args(b);
+int launch_propagate(viekf_batch* b, const double* d_u, const double* d_dt, const unsigned char* call_mask = nullptr) {
+  if (int rc = require_P(b, stream_mfma_ok(b) ? PForm::Lower : PForm::Full)) return rc;
+  StreamArgs a = make_args(b, call_mask);
   if (stream_mfma_ok(b)) {   // feature/feature part on the fp64 matrix cores: reads and writes the lower triangle only
     const size_t wlds = sizeof(double) * (size_t)WideLds(b->N, b->nxs).total;
     if (b->tune_stream_mfma != 2 && 3 * b->N <= 512 && wlds <= 158 * 1024) {   // the K = 24 record form, records in LDS
@@ -72,7 +72,7 @@ int launch_propagate(viekf_batch* b, const double* d_u, const double* d_dt) {
       hipLaunchKernelGGL((k_propagate_stream<512, true>), dim3(b->B), dim3(512), lds_propagate(b) + sizeof(double) * (9 * (size_t)b->N + 2),
                          b->stream, a, d_u, d_dt);
     }
-    set_level(b, 2);
+    b->book.wrote_live(PForm::Lower);
   } else
     hipLaunchKernelGGL((k_propagate_stream<kThreads, false>), dim3(b->B), dim3(kThreads), lds_propagate(b), b->stream, a, d_u,
                        d_dt);
@@ -114,7 +114,7 @@ int blocked_group(const viekf_batch* b, size_t* lds_bytes) {
 
 int launch_update(viekf_batch* b, const double* d_z, const int* d_slot, int M, const double* d_R, int r_mode,
                   int* d_res) {
-  if (int rc = ensure_full_P(b, 2)) return rc;   // (a fused launch may have left P packed)
+  if (int rc = require_P(b, PForm::Lower)) return rc;   // (a fused launch may have left P packed)
   StreamArgs a = make_args(b);
   long rsb = 0, rsm = 0;
   r_strides(r_mode, M, &rsb, &rsm);
@@ -129,9 +129,9 @@ int launch_update(viekf_batch* b, const double* d_z, const int* d_slot, int M, c
     static size_t have[64][6] = {};
     if (int rc = raise_dyn_lds({kern}, blds, have[b->device & 63][(bg == 32 ? 2 : (bg == 24 ? 1 : 0)) + (sv ? 3 : 0)])) return rc;
     hipLaunchKernelGGL(kern, dim3(b->B), dim3(512), blds, b->stream, a, d_z, d_slot, M, d_R, rsb, rsm, d_res);
-    set_level(b, 2);   // (reads and writes the lower triangle only)
+    b->book.wrote_live(PForm::Lower);   // (reads and writes the lower triangle only)
   } else {
-    if (int rc = ensure_full_P(b)) return rc;   // (the one-measurement kernel reads whole columns)
+    if (int rc = require_P(b, PForm::Full)) return rc;   // (the one-measurement kernel reads whole columns)
     hipLaunchKernelGGL(k_update_feat_stream<kThreads>, dim3(b->B), dim3(kThreads), lds_update(b), b->stream, a, d_z,
                        d_slot, M, d_R, rsb, rsm, d_res);
   }
@@ -183,45 +183,35 @@ int unpack_buffer(viekf_batch* b, double* x, double* P) {
   return VIEKF_OK;
 }
 
-int ensure_full_P(viekf_batch* b, int tolerate) {
-  if (b->upper_stale <= tolerate) return VIEKF_OK;
-  if (b->upper_stale == 3) {   // stage one: packed -> lower triangle valid
+// Brings the live P to at most the form the caller can take -- PForm::Full for whoever reads P whole, PForm::Lower for whoever
+// reads or writes elements of the lower triangle in place -- by the book's plan.  Touches the device only when it launches.
+int require_P(viekf_batch* b, PForm at_most) {
+  const PPlan plan = b->book.plan(at_most);
+  if (!plan.unpack && !plan.mirror) return VIEKF_OK;
+  HIP_TRY(hipSetDevice(b->device));
+  if (plan.unpack) {
     if (int rc = unpack_buffer(b, b->d_x, b->d_P)) return rc;
-    set_level(b, 2);
-    if (tolerate >= 2) return VIEKF_OK;
+    b->book.wrote_live(PForm::Lower);
   }
-  StreamArgs a = make_args(b);   // stage two: mirror the lower triangle up
-  const int nt = (b->n + 31) / 32;
-  hipLaunchKernelGGL(k_mirror_upper, dim3((unsigned)(nt * (nt + 1) / 2), b->B), dim3(256), 0, b->stream, a);
-  HIP_TRY(hipGetLastError());
-  set_level(b, 0);
+  if (plan.mirror) {
+    StreamArgs a = make_args(b);
+    const int nt = (b->n + 31) / 32;
+    hipLaunchKernelGGL(k_mirror_upper, dim3((unsigned)(nt * (nt + 1) / 2), b->B), dim3(256), 0, b->stream, a);
+    HIP_TRY(hipGetLastError());
+    b->book.wrote_live(PForm::Full);
+  }
   return VIEKF_OK;
-}
-// ... for the entry points that read all of P, ahead of their argument checks
-int need_full_P(viekf_batch* b) {
-  if (!b->upper_stale) return VIEKF_OK;
-  HIP_TRY(hipSetDevice(b->device));
-  return ensure_full_P(b);
-}
-// ... and for those that read or write elements of the lower triangle in place (init_feature, the diagnostics, the diagonal)
-int need_canonical_P(viekf_batch* b) {
-  if (b->upper_stale < 3) return VIEKF_OK;
-  HIP_TRY(hipSetDevice(b->device));
-  return ensure_full_P(b, 2);
 }
 // Every buffer of the batch canonical: before the ownership map changes (setup_resident) and before anything that moves single
 // filters between buffers (per-filter ring copies and live slots) -- a buffer must never hold filters of both forms.
 int canonicalize_all(viekf_batch* b) {
-  if (int rc = ensure_full_P(b, 2)) return rc;
-  for (int s = 0; s < (int)b->slot_packed.size(); s++)
-    if (b->slot_packed[(size_t)s]) {
-      if (int rc = unpack_buffer(b, slot_x(b, s), slot_P(b, s))) return rc;
-      b->slot_packed[(size_t)s] = 0;
-    }
-  if (b->home_packed && b->home_P) {
-    if (int rc = unpack_buffer(b, b->home_x, b->home_P)) return rc;
+  if (int rc = require_P(b, PForm::Lower)) return rc;
+  for (int i = 0; i <= b->hist_depth; i++) {   // (the ring's slots, then the batch's own buffers)
+    const int buf = i < b->hist_depth ? i : PBook::kHome;
+    if (!b->book.packed(buf)) continue;
+    if (int rc = unpack_buffer(b, buf_x(b, buf), buf_P(b, buf))) return rc;
+    b->book.unpacked(buf);
   }
-  b->home_packed = 0;
   return VIEKF_OK;
 }
 
@@ -297,21 +287,25 @@ constexpr int dbg_bits() { return 0; }
 bool use_tiles(const viekf_batch* b) { return b->tile_inst >= 0 && b->family != 1; }
 bool use_resident(const viekf_batch* b) { return (b->res_inst >= 0 || b->tile_inst >= 0) && b->family != 1; }
 
+// Do this batch's fused launches keep P PACKED from one launch to the next (nobody reads the canonical matrix in between)?  Not
+// the tile family, not under per-filter live slots (a buffer would end up mixed), VIEKF_TUNE_PACKED_P on, the image fits.
+bool keeps_packed(const viekf_batch* b) { return !use_tiles(b) && !b->book.per_filter() && b->tune_packed_p != 0 && packed_fits(b); }
+
 // one launch handles at most res_mcap(N) measurements; longer lists are chunked (P makes one extra HBM round trip per chunk)
 int launch_resident(viekf_batch* b, bool do_prop, const double* d_u, const double* d_dt, const double* d_z,
                     const int* d_slot, int M, const double* d_R, int r_mode, int* d_res, int dst_slot = -1, int KP = 1,
-                    const int* smap_out = nullptr, const int* kcount = nullptr) {
+                    const int* smap_out = nullptr, const int* kcount = nullptr, const unsigned char* call_mask = nullptr) {
   // dst_slot >= 0: the launch stores (x, P) into that slot of the history ring instead of in place (a single-chunk launch:
   // viekf_batch_propagate_to / _propagate_n_to); the caller makes the slot live afterwards (viekf_batch_select)
   // (the fused kernel loads the lower triangle only and stores the lower triangle only: no symmetrisation before or after)
-  // Form of P: the resident family keeps P PACKED from one launch to the next -- nobody reads the canonical matrix in between --
-  // where the image fits, the batch advances as a whole (no per-filter live slots, no participation mask: the buffer would end up
-  // mixed) and VIEKF_TUNE_PACKED_P is on.  The load form is whatever the live P is; everything else gets canonical P first.
-  const bool store_packed = !use_tiles(b) && !b->per_filter && !b->active_on && b->tune_packed_p != 0 && packed_fits(b);
-  if (use_tiles(b) || b->per_filter || b->active_on)
-    if (int rc = ensure_full_P(b, 2)) return rc;
-  int fmt = (b->upper_stale == 3 ? RES_FMT_LOAD_PACKED : 0) | (store_packed ? RES_FMT_STORE_PACKED : 0);
-  StreamArgs a = make_args(b);
+  // Form of P: packed where the batch keeps it packed and advances as a whole (a participation mask would leave the buffer
+  // mixed; call_mask comes with per-filter mode only).  The load form is whatever the live P is; everything else gets
+  // canonical P first.
+  const bool store_packed = keeps_packed(b) && !b->active_on;
+  if (use_tiles(b) || b->book.per_filter() || b->active_on)
+    if (int rc = require_P(b, PForm::Lower)) return rc;
+  int fmt = (b->book.live_form() == PForm::Packed ? RES_FMT_LOAD_PACKED : 0) | (store_packed ? RES_FMT_STORE_PACKED : 0);
+  StreamArgs a = make_args(b, call_mask);
   if (dst_slot >= 0) { a.x_out = slot_x(b, dst_slot); a.P_out = slot_P(b, dst_slot); }
   a.smap_out = smap_out;
   a.kcount = kcount;   // (per-filter propagate counts: the resident multi-propagate instances, KP > 1, read them; KP is their maximum)
@@ -337,12 +331,8 @@ int launch_resident(viekf_batch* b, bool do_prop, const double* d_u, const doubl
     //  launch stores canonical: a restored packed slot with the switch off, say)
     fmt = (fmt & ~RES_FMT_LOAD_PACKED) | (store_packed ? RES_FMT_LOAD_PACKED : 0);
   } while (m0 < M);
-  if (dst_slot >= 0) {   // another ring slot was written: its form is recorded, the caller makes it live
-    b->slot_packed[(size_t)dst_slot] = store_packed;
-    b->stale_ever = 2;
-  } else {
-    set_level(b, store_packed ? 3 : 2);
-  }
+  if (dst_slot >= 0) b->book.wrote_slot(dst_slot, store_packed);   // (the caller makes it live)
+  else b->book.wrote_live(store_packed ? PForm::Packed : PForm::Lower);
   return VIEKF_OK;
 }
 
