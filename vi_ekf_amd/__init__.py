@@ -10,3 +10,5 @@ from .seq import SeqVIEKF  # noqa: E402,F401
 from .klt import KLTTracker, track_frame  # noqa: E402,F401
 from . import diag  # noqa: E402,F401
 from .diag import consistency, innovation  # noqa: E402,F401
+from . import simbatch  # noqa: E402,F401
+from .simbatch import BatchSimulator, landmarks_like  # noqa: E402,F401
