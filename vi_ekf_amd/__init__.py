@@ -12,3 +12,5 @@ from . import diag  # noqa: E402,F401
 from .diag import consistency, innovation  # noqa: E402,F401
 from . import simbatch  # noqa: E402,F401
 from .simbatch import BatchSimulator, landmarks_like  # noqa: E402,F401
+from . import frame  # noqa: E402,F401
+from .frame import FrameIntake  # noqa: E402,F401

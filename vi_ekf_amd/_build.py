@@ -13,6 +13,7 @@ def sources():
     out.append(os.path.join(os.path.dirname(HERE), "include", "viekf_klt.h"))
     out.append(os.path.join(os.path.dirname(HERE), "include", "viekf_diag.h"))
     out.append(os.path.join(os.path.dirname(HERE), "include", "viekf_sim.h"))
+    out.append(os.path.join(os.path.dirname(HERE), "include", "viekf_frame.h"))
     return out
 
 

@@ -152,6 +152,13 @@ def lib():
         L.viekf_batch_restore.argtypes = [_vp, C.c_int32]
         L.viekf_batch_step.argtypes = [_vp, _vp, _vp, _vp, _vp, C.c_int32, _vp, C.c_int32, _vp, C.c_int]
         L.viekf_batch_step_n.argtypes = [_vp, C.c_int32, _vp, _vp, _vp, _vp, C.c_int32, _vp, C.c_int32, _vp, C.c_int]
+        # include/viekf_frame.h (vi_ekf_amd/frame.py)
+        L.viekf_frame_create.argtypes = [_vp, C.POINTER(_vp)]
+        L.viekf_frame_destroy.argtypes = [_vp]
+        L.viekf_frame_reset.argtypes = [_vp]
+        L.viekf_frame_set_tracked.argtypes = [_vp, _vp, C.c_int]
+        L.viekf_frame_tracked.argtypes = [_vp, _vp, _vp, C.c_int]
+        L.viekf_frame_intake.argtypes = [_vp, C.c_int32, _vp, _vp, _vp, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int]
         _lib = L
     return _lib
 

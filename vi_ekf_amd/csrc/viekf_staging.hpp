@@ -136,7 +136,7 @@ class Staged {
     return VIEKF_OK;
   }
 
-  static constexpr int kMaxOut = 4;
+  static constexpr int kMaxOut = 5;   // (viekf_frame_intake hands back five arrays)
   viekf_batch* b_;
   viekf_mem where_;
   struct Back { void* host; const void* dev; size_t bytes; } back_[kMaxOut];

@@ -1,0 +1,151 @@
+"""Python face of the device-resident frame intake (include/viekf_frame.h): what VIEKF_ROS::color_image_callback does with
+a tracked frame -- keep_only_features and its keyframe test, the id -> slot lookup, init_feature for new ids, the frame's
+FEAT updates in the reference's order -- for every filter of a BatchVIEKF, with the feature-id tables in device memory.
+Plumbing only: the numbers come from libviekf_hip.so (csrc/viekf_kernels_frame.hpp); there is no CPU fallback.
+
+Arguments are numpy arrays (host pointers, numpy results) or contiguous CUDA torch tensors on the batch's device (device
+pointers, torch results), by the rules of BatchVIEKF._arg; one call takes one kind.  With device tensors nothing crosses to
+the host: z, ids and depth are exactly what BatchSimulator.camera(device=True) and KLTTracker hand out.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import capi
+
+# every symbol include/viekf_frame.h declares (tests check the library exports exactly these)
+FRAME_SYMBOLS = ["viekf_frame_create", "viekf_frame_destroy", "viekf_frame_reset", "viekf_frame_set_tracked",
+                 "viekf_frame_tracked", "viekf_frame_intake"]
+MAX_M = 4096     # VIEKF_FRAME_MAX_M
+
+
+def _is_torch(a):
+    return hasattr(a, "data_ptr") and hasattr(a, "is_cuda")
+
+
+class FrameIntake:
+    """
+        fi = FrameIntake(batch)
+        out = fi.intake(z, ids, R_pix)         # dict(result [B][M], gated [B][M], gated_count [B], did_reset [B], edges [B][17])
+        ids, ln = fi.tracked()                  # [B][N] -1 padded in slot order (BatchSimulator.truth_state takes it), [B]
+    """
+
+    def __init__(self, batch):
+        self._L = capi.lib()
+        self._h = None
+        self.batch = batch      # (the batch must outlive the intake: it stays referenced from here)
+        self._alive()
+        h = C.c_void_p()
+        capi.check(self._L.viekf_frame_create(batch._h, C.byref(h)))
+        self._h = h
+
+    def _alive(self):
+        if getattr(self.batch, "_h", None) is None or not self.batch._h.value:
+            raise ValueError("the batch of this FrameIntake has been closed")
+
+    def close(self):
+        if self._h:
+            self._L.viekf_frame_destroy(self._h)   # (the tables can go after their batch has)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _handle(self):
+        if not self._h:
+            raise ValueError("this FrameIntake has been closed")
+        self._alive()
+        return self._h
+
+    def _empty(self, shape, dtype, device):
+        if device:
+            import torch
+            t = torch.empty(shape, dtype=getattr(torch, np.dtype(dtype).name), device="cuda:%d" % self.batch.device)
+            return t, C.c_void_p(t.data_ptr())
+        a = np.empty(shape, dtype=dtype)
+        return a, C.c_void_p(a.ctypes.data)
+
+    def _ready(self, device, sync):
+        """device outputs come from torch's caching allocator and the inputs may still be in torch's queue, while the
+        work runs on the batch's stream (as BatchSimulator does)"""
+        if device and sync:
+            import torch
+            torch.cuda.synchronize(self.batch.device)
+
+    def reset(self):
+        """no ids tracked, no keyframe list (pairs with BatchVIEKF.reset)"""
+        capi.check(self._L.viekf_frame_reset(self._handle()))
+
+    def set_tracked(self, ids):
+        """adopt a state written with BatchVIEKF.set_state / init_feature: ids [B][N], row b = len_features[b] distinct
+        ids >= 0, then -1 (host arrays are checked)"""
+        g = self.batch
+        h = self._handle()
+        g._keep = []
+        p, w = g._arg(ids, np.int32, (g.B, g.N), None)
+        self._ready(w == capi.DEVICE, True)
+        capi.check(self._L.viekf_frame_set_tracked(h, p, w))
+        if w == capi.DEVICE:
+            g.sync()
+        g._keep = []
+
+    def tracked(self, device=False):
+        """-> (ids [B][N] -1 padded in slot order, len [B])"""
+        g = self.batch
+        h = self._handle()
+        ids, pi = self._empty((g.B, g.N), np.int32, device)
+        ln, pl = self._empty((g.B,), np.int32, device)
+        self._ready(device, True)
+        capi.check(self._L.viekf_frame_tracked(h, pi, pl, capi.DEVICE if device else capi.HOST))
+        if device:
+            g.sync()
+        return ids, ln
+
+    def intake(self, z, ids, R, depth=None, active=None, sync=True):
+        """one frame per filter: z [B][M][2] NaN padded, ids [B][M] -1 padded, R (2,2), (B,2,2) or (B,M,2,2) indexed
+        [row, col], depth [B][M] or None, active [B] uint8 or None
+        -> dict(result [B][M], gated [B][M], gated_count [B], did_reset [B], edges [B][17]), where the inputs live.
+        With device tensors and sync=False the call returns once its work is queued on the batch's stream: inputs and
+        outputs are then the caller's to order (batch.sync(), or a stream shared with torch)."""
+        g = self.batch
+        h = self._handle()
+        g._keep = []
+        B = g.B
+        if len(ids.shape) != 2:
+            raise ValueError("ids must be [B][M]")
+        M = int(ids.shape[1])
+        pz, w = g._arg(z, np.float64, (B, M, 2), None)
+        pi, w = g._arg(ids, np.int32, (B, M), w)
+        Rshape = tuple(R.shape)
+        if Rshape == (2, 2):       # the ABI takes column-major 2x2
+            r_mode = 0
+            Rc = R.t().contiguous() if _is_torch(R) else np.ascontiguousarray(np.asarray(R, dtype=np.float64).T)
+        elif Rshape == (B, 2, 2):
+            r_mode = 1
+            Rc = R.transpose(1, 2).contiguous() if _is_torch(R) else np.ascontiguousarray(np.asarray(R, dtype=np.float64).transpose(0, 2, 1))
+        elif Rshape == (B, M, 2, 2):
+            r_mode = 2
+            Rc = R.transpose(2, 3).contiguous() if _is_torch(R) else np.ascontiguousarray(np.asarray(R, dtype=np.float64).transpose(0, 1, 3, 2))
+        else:
+            raise ValueError("R must be (2,2), (B,2,2) or (B,M,2,2)")
+        pR, w = g._arg(Rc, np.float64, tuple(Rc.shape), w)
+        pd, w = g._arg(depth, np.float64, (B, M), w)
+        pa, w = g._arg(active, np.uint8, (B,), w)
+        dev = w == capi.DEVICE
+        out = {}
+        out["result"], pres = self._empty((B, M), np.int32, dev)
+        out["gated"], pg = self._empty((B, M), np.int32, dev)
+        out["gated_count"], pgc = self._empty((B,), np.int32, dev)
+        out["did_reset"], pdr = self._empty((B,), np.uint8, dev)
+        out["edges"], pe = self._empty((B, 17), np.float64, dev)
+        self._ready(dev, sync)
+        capi.check(self._L.viekf_frame_intake(h, M, pz, pi, pd, pR, r_mode, pa, pres, pg, pgc, pdr, pe, w))
+        if dev and sync:
+            g.sync()
+        elif dev:
+            self._pending = (z, ids, Rc, depth, active)   # (re-laid-out R must outlive the queued work)
+        g._keep = []
+        return out
