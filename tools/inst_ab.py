@@ -4,7 +4,9 @@ library, alternating, and compare the files): per instance, at its largest featu
   mp_zu / mp_gen  viekf_batch_step_n with K = 3 propagates + N updates (the multi-propagate kernels)
   prop / prop_n   one propagate-only launch; step_n with K = 3 and no measurements
 HIP events around `reps` launches, `blocks` times; the figure kept is the median block, in microseconds per launch.
-usage: python tools/inst_ab.py OUT.json [B] [reps] [blocks]"""
+usage: python tools/inst_ab.py OUT.json [B] [reps] [blocks] [kinds] [instances]
+kinds / instances: comma-separated launch names / row indices to time (default: all) -- e.g. only the launches whose kernels a
+change touches."""
 import json
 import os
 import sys
@@ -18,6 +20,7 @@ import vi_ekf_amd as v  # noqa: E402
 from vi_ekf_amd import capi, scene  # noqa: E402
 
 K, STEPS = 3, 6
+KINDS = ("zu", "gen", "mp_zu", "mp_gen", "prop", "prop_n")
 
 
 def main():
@@ -25,9 +28,12 @@ def main():
     B = int(sys.argv[2]) if len(sys.argv) > 2 else 1024
     reps = int(sys.argv[3]) if len(sys.argv) > 3 else 30
     blocks = int(sys.argv[4]) if len(sys.argv) > 4 else 3
+    kinds = sys.argv[5].split(",") if len(sys.argv) > 5 and sys.argv[5] else list(KINDS)
+    insts = [int(i) for i in sys.argv[6].split(",")] if len(sys.argv) > 6 and sys.argv[6] else range(len(NMAX))
+    assert set(kinds) <= set(KINDS), kinds
     dev = torch.device("cuda:0")
     res = {}
-    for inst in range(len(NMAX)):
+    for inst in insts:
         N = NMAX[inst]
         sc = scene.make_scene(B, N, STEPS, seed=3)
         d = {k: torch.tensor(sc[k], device=dev) for k in ("u", "z", "dt", "slot", "R")}
@@ -36,7 +42,7 @@ def main():
         pix = torch.tensor(np.ascontiguousarray(sc["pix"].transpose(1, 0, 2)), device=dev)
         nan = torch.full((B,), float("nan"), dtype=torch.float64, device=dev)
         out_codes = torch.empty((B, N), dtype=torch.int32, device=dev)
-        for name in ("zu", "gen", "mp_zu", "mp_gen", "prop", "prop_n"):
+        for name in kinds:
             g = v.BatchVIEKF(B, N, sc["params"])
             g.set_tuning(capi.TUNE_RES_INSTANCE, inst)
             if name.endswith("gen"):

@@ -28,8 +28,11 @@ def d(a, b): return int(t[b] - t[a])
 print("common prologue (62->63 incl barrier)", d(62, 63))
 print("service: B0 wait", d(0, 1), " body phase", d(1, 2), " B1p wait", d(2, 3), " feature phase", d(3, 4), " B2p wait", d(4, 5),
       " body step+fix", d(5, 6), " B3p wait", d(6, 7), " B4p wait (GEMM)", d(7, 8), " first h_feat", d(8, 9), " B1 wait", d(9, 10))
-print("worker : load->B0", d(63, 64), " B0 wait", d(64, 65), " to B3p", d(65, 66), " B3p wait", d(66, 67), " local3x3", d(67, 68),
-      " GEMM", d(68, 69), " strips", d(69, 70), " B4p+extract->B1", d(70, 71))
+# (stamp 74: the blocks of P have landed -- a diagnostic build waits for them behind B3p.  Where the block loads stay in flight across
+#  the set-up, `LDS part + issue->B0` does not contain their round trip and `wait for blocks` is what is left of it behind B3p.)
+print("worker : LDS part + issue->B0", d(63, 64), " B0 wait", d(64, 65), " set-up to B3p", d(65, 66), " B3p wait", d(66, 67),
+      " wait for blocks", d(67, 74), " local3x3", d(74, 68), " GEMM", d(68, 69), " strips", d(69, 70), " B4p+extract->B1", d(70, 71))
+print("worker : B0 falls at", d(63, 65), " B3p falls at", d(63, 67), " blocks first used at", d(63, 74), " (ticks after the prologue)")
 # one barrier per update (B1).  service: 16+4it+{0: phase inputs loaded, 1: rotation vector ready, 2: gain rows of the next
 # measurement written (before B1), 3: after B1}; 128+4it+{0,1}: around the manifold correction.  worker (thread 0):
 # 80+4it+{1: phase top, 2: before B1, 3: after B1}; 160+4it+{0: blocks swept, 1: raw columns published + counted in}.

@@ -175,6 +175,18 @@ __device__ __forceinline__ void res_words(const int* __restrict__ resmap, int t,
 // <8,6> at the register file's end (its propagate-only launch +1.8 %, more spilled dwords).  Those compile to the instruction
 // stream they had before (profiles/serial_loads/).
 constexpr bool res_batched_loads(int RB, int NW) { return NW != 7 && RB != 8; }
+// Which instances spread the block loads of P over the propagate's set-up and first wait for them behind B3p (res_worker, switch
+// SU): the single-propagate kernels of <4,3>, <6,3>, <7,3> and <5,6> -- the instances that timed faster or equal with it, each
+// against the parent (profiles/setup_under_load/instances_ab.md).  <2,1>, <2,2>, <3,2> (two or three blocks per thread: little to
+// spread, one more batch of address arithmetic) measured 1 - 5 % SLOWER, <5,3> and <7,6> slower beyond their spread in the
+// unit-Lambda step (+1.4 %, +0.5 %): they keep the old order.  So do the multi-propagate kernels -- their set-up reads sqrt(Qu) from
+// memory, a vector load that would drain the blocks, and only the first of K trips has loads in flight -- and <6,6> at the register
+// file's end (254 VGPRs: with its blocks in flight across the set-up, all issued ahead of B0, its unit-Lambda kernel spilled two
+// registers to scratch; the spread form was not tried on it).  An instance that keeps the old order compiles to the instruction
+// stream it had before.
+constexpr bool res_setup_under_load(int RB, int NW, bool MP) {
+  return res_batched_loads(RB, NW) && !MP && ((NW == 3 && (RB == 4 || RB == 6 || RB == 7)) || (NW == 6 && RB == 5));
+}
 // false = not owned (then I = J = 0: every LDS / global read stays in range, results are never stored)
 __device__ __forceinline__ bool res_word_blk(int e, int& I, int& J) {
   I = e & 0xff;

@@ -119,8 +119,10 @@ __device__ RES_INLINE void res_fix_depth(double* xf, const DevParams* p, double*
 // Barriers B1p, B2p, B2q inside; the caller continues with B3p.
 // LDSC: sqrt(Qu) from the resident family's LDS copy (ResLds::sm, RES_SM_SQRTQU) -- read from memory, the constant's round
 // trip sits inside an interval the whole workgroup waits on, once per interval.  (The tile family's sm has no such words.)
-template <int TW, bool LDSC = false>
-__device__ __forceinline__ void res_prop_setup(const StreamArgs& a, const ResShared& S, int tid) {
+// hook(k), k = 0 .. 2 as std::integral_constant: called behind B1p, B2p and B2q (the worker's spread block loads)
+struct ResNoHook { template <class K> __device__ __forceinline__ void operator()(K) const {} };
+template <int TW, bool LDSC = false, class Hook = ResNoHook>
+__device__ __forceinline__ void res_prop_setup(const StreamArgs& a, const ResShared& S, int tid, const Hook& hook = Hook()) {
   const int nf = S.nf, N = S.N;
   const DevParams& prm = *a.dp;
   double* Pbc = S.Pbc; double* Pbb = S.Pbb;
@@ -128,6 +130,7 @@ __device__ __forceinline__ void res_prop_setup(const StreamArgs& a, const ResSha
   double* Phibb = S.Phibb; double* Mbb = S.Mbb; double* Gdb = S.Gdb; double* T16 = S.T16;
   __syncthreads();  // B1p : body Jacobian, raw feature blocks and Phi_ff ready (service), and this propagate's dt
   const double dt = S.sm[42];
+  hook(std::integral_constant<int, 0>{});
 
   // ---- [B1p..B2p]
   for (int e = tid; e < nf; e += TW) res_feature_expand_row(e / 3, e % 3, dt, Z, S.Gb, S.AvG, LDSC ? S.sm + RES_SM_SQRTQU : prm.sqrtQu);
@@ -164,6 +167,7 @@ __device__ __forceinline__ void res_prop_setup(const StreamArgs& a, const ResSha
     pc[32] = ff[6] * p0 + ff[7] * p1 + ff[8] * p2;
   }
   __syncthreads();  // B2p
+  hook(std::integral_constant<int, 1>{});
 
   // ---- [B2p..B2q]
   for (int e = tid; e < 256; e += TW) {
@@ -194,6 +198,7 @@ __device__ __forceinline__ void res_prop_setup(const StreamArgs& a, const ResSha
     S.Pi[e] = v;
   }
   __syncthreads();  // B2q
+  hook(std::integral_constant<int, 2>{});
 
   // ---- [B2q..B3p]
   // Ut = [D | V] [Pi / 2 ; Psi^T]  (nf x 25)(25 x 9) on the matrix cores, one 16-row tile per wave and turn, 7 k-steps (as

@@ -125,8 +125,15 @@ __device__ __forceinline__ void res_body_items(const ResShared& S, const double*
 // (The service wave takes no share of the body-column items: with the tile map its chain is the longest wave of an update and
 //  every share > 0 measured slower -- N = 50, B = 1024: 0 / N / 2 N items -> 0.348 / 0.347 / 0.353 ms per step.)
 // BL: the instance issues its launch-constant loads in batches (res_batched_loads, viekf_resident_common.hpp)
+// SU: the block loads of P are in flight across B0 and the propagate's set-up (res_setup_under_load, same file), and their issue is
+//     spread over the set-up's barrier intervals: chunk k of 4 = blocks [RB k / 4, RB (k + 1) / 4), chunk 0 ahead of B0, chunks 1 .. 3
+//     behind B1p, B2p and B2q (the hook of res_prop_setup) -- with all of them issued at once a wave stands at the issue while the
+//     memory system works off the batch of every workgroup on the chip.  Everything the set-up reads is in LDS before the first of
+//     them is issued, and nothing between that and the barrier B3p touches `pb` or waits for a vector memory instruction younger
+//     than the ownership words -- loads return in order, so a wait for any later one would drain them
 template <int RB, int TW, bool MP, int T = TW + 64, bool ZU = false, bool BL = true>
 __device__ __forceinline__ void res_worker(const StreamArgs& a, const ResShared& S, int tid) {
+  constexpr bool SU = res_setup_under_load(RB, TW / 64, MP);
   const int N = S.N, n = S.n, ld = a.ld, nf = S.nf, len = S.len;
   double* P = a.P + S.si * n * ld;
   // SYMMETRIC ownership: of each unordered pair of feature blocks {I,J} only one is kept (I >= J); which thread keeps it in
@@ -156,6 +163,19 @@ __device__ __forceinline__ void res_worker(const StreamArgs& a, const ResShared&
   // the propagate (7 blocks per thread), the select costs none in the update loop.  Packed, a wave's 8-byte loads cover 1 KB
   // contiguous, the two halves of a pair from the same lines.
   const bool ldp = (S.fmt & RES_FMT_LOAD_PACKED) != 0;
+  // Lambda for feature/feature blocks: one 3x3 constant (lambda_feat identical for all slots), kept in SGPRs
+  // (vector loads of launch constants: SU reads them, and the LDS-resident part of a canonical P, AHEAD of the block loads -- the
+  //  same statements as behind them; a load -> ds_write loop behind 63 outstanding loads would wait for all of them)
+  double Lff[9];
+  bool partial_su = false;
+  if (SU) {
+    const double lf[3] = {a.lambda[16], a.lambda[17], a.lambda[18]};
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+      for (int s = 0; s < 3; s++) Lff[r * 3 + s] = uniform_f64(prm.use_partial_update ? (lf[s] + lf[r] - lf[r] * lf[s]) : 1.0);
+    partial_su = prm.use_partial_update != 0;
+  }
   if (ldp) {   // the LDS-resident part, as it sat in LDS: 16 bytes per lane
     const int t = opaque(tid_);
     constexpr ResPack K(0, RB, TW / 64);
@@ -164,12 +184,34 @@ __device__ __forceinline__ void res_worker(const StreamArgs& a, const ResShared&
     const v2f64* gb = reinterpret_cast<const v2f64*>(P + K.pbc + 48 * N);
     for (int e = t; e < 128; e += TW) *reinterpret_cast<v2f64*>(Pbb + 2 * e) = gb[e];
   }
+  if (SU) {
+    for (int e = tid; !ldp && e < nf * 16; e += TW) {
+      const int k = e / nf, row = e - k * nf;
+      Pbc[row * 16 + k] = P[(16 + row) + (long)k * ld];
+    }
+    for (int e = tid; !ldp && e < 256; e += TW) {
+      const int r = e & 15, c = e >> 4;
+      Pbb[r * 16 + c] = P[max(r, c) + (long)min(r, c) * ld];
+    }
+  }
+  // (SU: the words of the block load serve the local transforms and the contraction too, and Qx of the diagonal block is read
+  //  with them -- a load issued behind the blocks would wait for a free place in the 6-bit counter, that is for the blocks)
+  int ws[SU ? RB : 1];
+  double qs[3];
   {
     const int tq = opaque(tid_);
     int ew[RB];   // all words first: the 9 RB loads of P are then in flight together, behind counted waits on the words
     if (BL) res_words<RB, TW>(resmap, tq, ew);
+    if (SU) {
 #pragma unroll
-    for (int ia = 0; ia < RB; ia++) {
+      for (int ia = 0; ia < RB; ia++) ws[ia] = ew[ia];
+      if (S.do_prop) {
+#pragma unroll
+        for (int r = 0; r < 3; r++) qs[r] = a.Qx[16 + 3 * min(tq, N - 1) + r];
+      }
+    }
+#pragma unroll
+    for (int ia = 0; ia < (SU ? RB / 4 : RB); ia++) {
       int I, J;
       blk(ew, tq, ia, I, J);
       // only the lower triangle of P is valid in memory (see the store): a block above the diagonal is read as the transpose
@@ -191,17 +233,42 @@ __device__ __forceinline__ void res_worker(const StreamArgs& a, const ResShared&
         }
     }
     // body columns -> LDS (coalesced along rows)
-    for (int e = tid; !ldp && e < nf * 16; e += TW) {
+    for (int e = tid; !SU && !ldp && e < nf * 16; e += TW) {
       const int k = e / nf, row = e - k * nf;
       Pbc[row * 16 + k] = P[(16 + row) + (long)k * ld];
     }
     // (the body block is kept EXACTLY symmetric, like every other part of P here -- see sym_diag below: both copies of a pair
     //  are loaded from the lower triangle)
-    for (int e = tid; !ldp && e < 256; e += TW) {
+    for (int e = tid; !SU && !ldp && e < 256; e += TW) {
       const int r = e & 15, c = e >> 4;
       Pbb[r * 16 + c] = P[max(r, c) + (long)min(r, c) * ld];
     }
   }
+
+  // SU: chunk kc + 1 of the block loads (the statements of the loop above), from the set-up's hook
+  auto issue_chunk = [&](auto kc) {
+    constexpr int k = decltype(kc)::value + 1, lo = RB * k / 4, hi = RB * (k + 1) / 4;
+    const int tq = opaque(tid_);
+#pragma unroll
+    for (int ia = lo; ia < hi; ia++) {
+      int I, J;
+      res_word_blk(ws[SU ? ia : 0], I, J);
+      const bool up = I < J;
+      const int br = 16 + 3 * (up ? J : I), bc = 16 + 3 * (up ? I : J);
+      const unsigned cbase = (unsigned)(br + bc * ld);
+      const unsigned base = ldp ? 2u * (unsigned)tq : cbase, base1 = ldp ? (unsigned)tq : cbase;
+#pragma unroll
+      for (int s = 0; s < 3; s++)
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+          const int rr = (I == J) ? max(r, s) : (up ? s : r), cc = (I == J) ? min(r, s) : (up ? r : s);
+          constexpr ResPack K(0, RB, TW / 64);
+          const int q = ia * 9 + r * 3 + s;
+          const unsigned offp = (unsigned)K.elem(q, 0), offc = (unsigned)(rr + cc * ld);
+          pb[ia][r * 3 + s] = P[((q < 2 * K.npair) ? base : base1) + (ldp ? offp : offc)];
+        }
+    }
+  };
 
   // P is kept EXACTLY symmetric.  Off-diagonal feature blocks and the feature/body strips are symmetric by ownership (one
   // copy, mirrored at store time); the diagonal blocks (and the body block, in LDS) hold both triangles, and their lower one
@@ -212,17 +279,16 @@ __device__ __forceinline__ void res_worker(const StreamArgs& a, const ResShared&
   auto sym_diag = [&]() {
     if (own_diag) { pb[0][3] = pb[0][1]; pb[0][6] = pb[0][2]; pb[0][7] = pb[0][5]; }
   };
-  sym_diag();
-  // Lambda for feature/feature blocks: one 3x3 constant (lambda_feat identical for all slots), kept in SGPRs
-  double Lff[9];
-  {
+  // (SU: a use of the blocks -- it follows B3p, or the propagate section of a launch without a propagate)
+  if (!SU) {
+    sym_diag();
     const double lf[3] = {a.lambda[16], a.lambda[17], a.lambda[18]};
 #pragma unroll
     for (int r = 0; r < 3; r++)
 #pragma unroll
       for (int s = 0; s < 3; s++) Lff[r * 3 + s] = uniform_f64(prm.use_partial_update ? (lf[s] + lf[r] - lf[r] * lf[s]) : 1.0);
   }
-  const bool partial = prm.use_partial_update != 0;
+  const bool partial = SU ? partial_su : prm.use_partial_update != 0;
   int par = 0;  // fix_depth mailbox parity (mirrors the service wave)
   constexpr int NSV = (T - TW) / 64;   // service waves: with one, the second wave's flag words are not read at all
   auto fix_word = [&](int mb) -> double { return (NSV > 1) ? S.sm[40 + mb] + S.sm[36 + mb] : S.sm[40 + mb]; };
@@ -250,7 +316,12 @@ __device__ __forceinline__ void res_worker(const StreamArgs& a, const ResShared&
     //  clamp only keeps the load of a thread without a diagonal block inside the array.)
     int ep[RB];
     double qd[3];
-    if (BL) {
+    if (SU) {
+#pragma unroll
+      for (int ia = 0; ia < RB; ia++) ep[ia] = ws[SU ? ia : 0];
+#pragma unroll
+      for (int r = 0; r < 3; r++) qd[r] = qs[r];
+    } else if (BL) {
       const int tq = opaque(tid_);
       res_words<RB, TW>(resmap, tq, ep);
 #pragma unroll
@@ -259,10 +330,16 @@ __device__ __forceinline__ void res_worker(const StreamArgs& a, const ResShared&
     // (multi-propagate instances: sqrt(Qu) stays a memory operand of the set-up -- cached after the first propagate; the LDS
     //  operand cost them 16 .. 22 scalar-register reloads per update in the service loop)
     if (MP || !BL) res_prop_setup<TW>(a, S, tk);
+    else if (SU) res_prop_setup<TW, true>(a, S, tk, issue_chunk);
     else res_prop_setup<TW, true>(a, S, tk);
     RES_STAMP(S, tid == 0, 66);
     __syncthreads();  // B3p
     RES_STAMP(S, tid == 0, 67);
+#ifdef VIEKF_STAMPS
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (diagnostic build: the wait for the blocks, apart from the transforms)
+#endif
+    RES_STAMP(S, tid == 0, 74);
+    if (SU) sym_diag();   // the first use of the blocks: the wait for their loads falls here
 
     // ---- local 3x3 transforms  Phi_ff[I] (P[I,J] Phi_ff[J]^T) (+ Qx on the diagonal), in place with 3 temporaries:
     //      first each row times Phi_ff[J]^T, then each column times Phi_ff[I]  (keeps the register peak low)
@@ -360,6 +437,12 @@ __device__ __forceinline__ void res_worker(const StreamArgs& a, const ResShared&
     }
    }
 
+  if (SU && !S.do_prop) {   // no propagate: the rest of the blocks here; their wait falls before the Pd hand-over and the first extraction
+    issue_chunk(std::integral_constant<int, 0>{});
+    issue_chunk(std::integral_constant<int, 1>{});
+    issue_chunk(std::integral_constant<int, 2>{});
+    sym_diag();
+  }
   // block indices of this thread, computed once (symmetric ownership left enough registers to keep them)
   int Ib[RB], Jb[RB];
   bool vb[RB];
