@@ -4,8 +4,8 @@
  * global id -> local slot lookup of add_measurement(FEAT, id), init_feature for ids the filter has not seen, and the
  * frame's FEAT updates -- for every filter of a batch, with the feature-id bookkeeping in device memory.  This is the
  * ZERO-DELAY route: the frame belongs to the time the filter is at.  Delayed frames, rewind and replay remain the host
- * sequencer's job (viekf_seq_*), and so does composing the keyframe edges into a global node pose.  DESIGN.md §12 has
- * the kernels.
+ * sequencer's job (viekf_seq_*); composing the keyframe edges into a global node pose is viekf_node.h's.  DESIGN.md §12
+ * has the kernels.
  *
  * Conventions are those of viekf.h: every call returns VIEKF_OK or a negative viekf_status, nothing throws,
  * viekf_last_error() holds the message of the last failing call of this thread, there is no CPU fallback, `where` says

@@ -14,3 +14,5 @@ from . import simbatch  # noqa: E402,F401
 from .simbatch import BatchSimulator, landmarks_like  # noqa: E402,F401
 from . import frame  # noqa: E402,F401
 from .frame import FrameIntake  # noqa: E402,F401
+from . import node  # noqa: E402,F401
+from .node import NodeGraph  # noqa: E402,F401

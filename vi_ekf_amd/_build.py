@@ -14,6 +14,7 @@ def sources():
     out.append(os.path.join(os.path.dirname(HERE), "include", "viekf_diag.h"))
     out.append(os.path.join(os.path.dirname(HERE), "include", "viekf_sim.h"))
     out.append(os.path.join(os.path.dirname(HERE), "include", "viekf_frame.h"))
+    out.append(os.path.join(os.path.dirname(HERE), "include", "viekf_node.h"))
     return out
 
 

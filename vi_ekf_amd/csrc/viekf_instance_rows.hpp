@@ -60,6 +60,9 @@ struct ResPack {
       : TW(64 * NW), npair(9 * RB / 2), single(2 * (9 * RB / 2) * 64 * NW), pbc(single + ((9 * RB) & 1) * 64 * NW),
         pbb(pbc + 48 * N), total(pbc + 48 * N + 256) {}
   constexpr int elem(int q, int t) const { return q < 2 * npair ? 2 * ((q >> 1) * TW + t) + (q & 1) : single + t; }
+  // element (r, c), r >= c, of the body block P[0..16, 0..16]: Pbb is row-major, and its entry [r][c] is what an unpack stores
+  // at row r of column c (viekf_node_global reads its 21 elements through this, viekf_capi.hip)
+  constexpr int body(int r, int c) const { return pbb + 16 * r + c; }
   constexpr bool fits(int n, int ld) const { return (long)total <= (long)n * ld; }
 };
 

@@ -1472,6 +1472,16 @@ __global__ __launch_bounds__(T) void k_keep_features(StreamArgs a, const unsigne
 // {t(3), q_yaw(4), cov_pos(9, column-major), cov_yaw} of the relative pose before the reset, for the caller's global-pose
 // bookkeeping (:58-62,125-126,147-149 -- the Xformd algebra of the reference's `geometry` dependency stays with the caller).
 // ------------------------------------------------------------------------------------------------
+// The yaw part of an attitude, as the reset takes it out of the state and hands it to the node frame: stated once, for the
+// edge below and for the node graph's true node (viekf_kernels_node.hpp), which applies the same map to the truth.
+__device__ __forceinline__ double q_yaw_dev(const double* q) {                             // src/quat.cpp:221-224
+  const double qw = q[0], qx = q[1], qy = q[2], qz = q[3];
+  return atan2(2.0 * (qw * qz + qx * qy), 1.0 - 2.0 * (qy * qy + qz * qz));
+}
+__device__ __forceinline__ void q_from_yaw_dev(double yaw, double* o) {                   // from_euler(0,0,yaw), :150-165
+  o[0] = cos(yaw / 2.0); o[1] = 0.0; o[2] = 0.0; o[3] = sin(yaw / 2.0);
+}
+
 template <int T>
 __global__ __launch_bounds__(T) void k_keyframe_reset(StreamArgs a, const unsigned char* __restrict__ mask,
                                                       double* __restrict__ edge_all) {
@@ -1483,7 +1493,7 @@ __global__ __launch_bounds__(T) void k_keyframe_reset(StreamArgs a, const unsign
   double* P = a.P + a.si(b) * n * ld;
   const double* q = xg + xATT;
   const double qw = q[0], qx = q[1], qy = q[2], qz = q[3];
-  const double yaw = atan2(2.0 * (qw * qz + qx * qy), 1.0 - 2.0 * (qy * qy + qz * qz));     // src/quat.cpp:221-224
+  const double yaw = q_yaw_dev(q);
   const double roll = atan2(2.0 * (qw * qx + qy * qz), 1.0 - 2.0 * (qx * qx + qy * qy));    // :211-214
   const double pitch = asin(2.0 * (qw * qy - qz * qx));                                     // :216-219
   const double cp = cos(roll), sp = sin(roll), tt = tan(pitch);                             // vi_ekf_kfr.cpp:134-136
@@ -1491,7 +1501,7 @@ __global__ __launch_bounds__(T) void k_keyframe_reset(StreamArgs a, const unsign
   if (edge_all && tid == 0) {
     double* e = edge_all + (long)b * 17;
     for (int i = 0; i < 3; i++) e[i] = xg[xPOS + i];
-    e[3] = cos(yaw / 2.0); e[4] = 0.0; e[5] = 0.0; e[6] = sin(yaw / 2.0);                   // from_euler(0,0,yaw), :150-165
+    q_from_yaw_dev(yaw, e + 3);
     for (int j = 0; j < 3; j++)
       for (int i = 0; i < 3; i++) e[7 + i + 3 * j] = P[(dxPOS + i) + (long)(dxPOS + j) * ld];
     e[16] = P[(dxATT + 2) + (long)(dxATT + 2) * ld];
