@@ -80,3 +80,31 @@ def test_argument_validation_without_device():
     p = capi.Params.from_dict({})
     assert L.viekf_batch_create(0, 3, C.byref(p), 0, C.byref(out)) == capi.ERR_INVALID
     assert b"batch" in L.viekf_last_error()
+
+
+def test_r_colmajor_transposes_every_shape_of_R():
+    """_dev.r_colmajor (BatchVIEKF._meas_args, FrameIntake.intake): R indexed [row, col] -> the ABI's column-major 2x2 and r_mode"""
+    from vi_ekf_amd._dev import r_colmajor
+    B, M = 2, 3
+    rng = np.random.default_rng(5)
+    cases = [(rng.normal(size=(2, 2)), 0), (rng.normal(size=(B, 2, 2)), 1), (rng.normal(size=(B, M, 2, 2)), 2)]
+    for R, mode in cases:
+        want = np.empty_like(R)
+        want[..., 0, 0], want[..., 0, 1], want[..., 1, 0], want[..., 1, 1] = R[..., 0, 0], R[..., 1, 0], R[..., 0, 1], R[..., 1, 1]
+        assert not np.array_equal(want, R)          # (non-symmetric: a missing transpose shows)
+        Rc, r_mode = r_colmajor(R, B, M)
+        assert r_mode == mode and Rc.dtype == np.float64 and Rc.flags.c_contiguous and np.array_equal(Rc, want)
+        Rc, r_mode = r_colmajor(R.astype(np.float32), B, M)     # converted like every other argument
+        assert r_mode == mode and Rc.dtype == np.float64 and np.array_equal(Rc, want.astype(np.float32).astype(np.float64))
+    for bad in (np.eye(3), np.zeros((B + 1, 2, 2)), np.zeros((B, M + 1, 2, 2)), np.zeros((2,))):
+        with pytest.raises(ValueError, match="R must"):
+            r_colmajor(bad, B, M)
+    try:
+        import torch
+    except ImportError:      # (the numpy half above stands on its own)
+        return
+    for R, mode in cases:
+        Rc, r_mode = r_colmajor(torch.from_numpy(R), B, M)
+        assert r_mode == mode and Rc.is_contiguous() and np.array_equal(Rc.numpy(), np.swapaxes(R, -1, -2))
+    with pytest.raises(ValueError, match="R must"):
+        r_colmajor(torch.zeros(3, 3), B, M)

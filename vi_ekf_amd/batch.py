@@ -10,10 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-
-
-def _is_torch(a):
-    return hasattr(a, "data_ptr") and hasattr(a, "is_cuda")
+from ._dev import is_torch, r_colmajor
 
 
 class BatchVIEKF:
@@ -45,7 +42,7 @@ class BatchVIEKF:
         """-> (pointer, where).  All array arguments of one call must live on the same side."""
         if a is None:
             return None, where
-        if _is_torch(a):
+        if is_torch(a):
             import torch
             want = {np.float64: torch.float64, np.int32: torch.int32, np.uint8: torch.uint8, np.uint32: torch.int32}[dtype]
             if not a.is_cuda or a.dtype != want or not a.is_contiguous():
@@ -64,7 +61,7 @@ class BatchVIEKF:
         return C.c_void_p(arr.ctypes.data), capi.HOST
 
     def _out(self, a, dtype, shape, where):
-        if _is_torch(a):
+        if is_torch(a):
             return self._arg(a, dtype, shape, where)
         if a.dtype != dtype or not a.flags.c_contiguous or a.shape != tuple(shape):
             raise ValueError("output array must be C-contiguous %s of shape %s" % (dtype, shape))
@@ -163,21 +160,9 @@ class BatchVIEKF:
         M = int(slot.shape[1])
         pz, w = self._arg(z, np.float64, (self.B, M, 2), None)
         ps, w = self._arg(slot, np.int32, (self.B, M), w)
-        Rshape = tuple(R.shape)
-        if Rshape == (2, 2):
-            r_mode = 0
-            # the ABI takes column-major 2x2; a symmetric R is the same either way, transpose to be exact
-            R = R.t().contiguous() if _is_torch(R) else np.ascontiguousarray(np.asarray(R, dtype=np.float64).T)
-        elif Rshape == (self.B, 2, 2):
-            r_mode = 1
-            R = R.transpose(1, 2).contiguous() if _is_torch(R) else np.ascontiguousarray(np.asarray(R).transpose(0, 2, 1))
-        elif Rshape == (self.B, M, 2, 2):
-            r_mode = 2
-            R = R.transpose(2, 3).contiguous() if _is_torch(R) else np.ascontiguousarray(np.asarray(R).transpose(0, 1, 3, 2))
-        else:
-            raise ValueError("R must be (2,2), (B,2,2) or (B,M,2,2)")
+        R, r_mode = r_colmajor(R, self.B, M)
         pR, w = self._arg(R, np.float64, tuple(R.shape), w)
-        if _is_torch(R):
+        if is_torch(R):
             self._keep.append(R)
         if result is None:
             if w == capi.DEVICE:

@@ -1,4 +1,5 @@
-// viekf_batch.hpp -- the batch handle of the C ABI (include/viekf.h), the error plumbing and the handle's small accessors.
+// viekf_batch.hpp -- the batch handle of the C ABI (include/viekf.h) and the handle's small accessors (the error plumbing and
+// the owner of its device memory are viekf_hostkit.hpp).
 // Pulls in viekf_kernels_stream.hpp (StreamArgs), which defines kernels: for the one HIP translation unit, viekf_capi.hip.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -9,7 +10,7 @@
 #include <vector>
 
 #include "../../include/viekf.h"
-#include "viekf_host.hpp"
+#include "viekf_hostkit.hpp"
 #include "viekf_kernels_stream.hpp"
 #include "viekf_pform.hpp"
 
@@ -20,6 +21,7 @@ struct viekf_batch {
   viekf_params params;
   hipStream_t stream = nullptr;
   bool own_stream = false;
+  DevOwner own;   // every device buffer below (hipMalloc); the pinned ring h_pin is the handle's own
   double *d_x = nullptr, *d_P = nullptr, *d_Qx = nullptr, *d_lambda = nullptr, *d_ws = nullptr, *d_x0 = nullptr,
          *d_Pdiag = nullptr;
   int* d_len = nullptr;
@@ -68,19 +70,10 @@ struct viekf_batch {
   // viekf_diag_consistency where the packed triangle does not fit the LDS: allocated on first use, at most 256 MiB while one
   // filter's triangle fits that (the batch is processed in chunks of filters)
   double* d_diag_ws = nullptr;
-  size_t diag_ws_bytes = 0;
+  size_t diag_ws_cap = 0;      // doubles
 };
 
 namespace {
-
-inline int fail(int code, const std::string& msg) { return viekf::set_last_error(code, msg); }
-
-#define HIP_TRY(expr)                                                                                  \
-  do {                                                                                                 \
-    hipError_t e_ = (expr);                                                                            \
-    if (e_ != hipSuccess)                                                                              \
-      return fail(VIEKF_ERR_HIP, std::string(#expr) + " failed: " + hipGetErrorString(e_));            \
-  } while (0)
 
 int check_batch(const viekf_batch* b) {
   if (!b) return fail(VIEKF_ERR_INVALID, "null batch handle");

@@ -1,6 +1,7 @@
 // viekf_capi.hip -- the entry points of the C ABI declared in include/viekf.h (libviekf_hip.so), and nothing else: the batch
 // handle is viekf_batch.hpp, kernel choice and launches viekf_dispatch.hpp, argument staging viekf_staging.hpp, the ownership
-// map viekf_resmap.cpp.  The one HIP translation unit of the host side.  No CPU fallback exists on purpose.
+// map viekf_resmap.cpp; the batch's companions (diagnostics, frame intake, node graph) are viekf_capi_*.hpp, included at the
+// end.  The one HIP translation unit of the host side.  No CPU fallback exists on purpose.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -129,26 +130,23 @@ int viekf_batch_create(int32_t batch, int32_t num_features, const viekf_params* 
   for (int i = 0; i < 6; i++) d.sqrtQu[i] = std::sqrt(p->Qu[i] > 0.0 ? p->Qu[i] : 0.0);
   const WsLayout L(b->N, b->n);
   b->ws_stride = L.total;
-#define ALLOC(ptr, bytes)                                                        \
-  do {                                                                           \
-    hipError_t e_ = hipMalloc(&(ptr), (bytes));                                  \
-    if (e_ != hipSuccess) {                                                      \
-      viekf_batch_destroy(b);                                                    \
-      return fail(VIEKF_ERR_HIP, std::string("hipMalloc failed: ") + hipGetErrorString(e_)); \
-    }                                                                            \
-  } while (0)
-  ALLOC(b->home_x, sizeof(double) * (size_t)batch * b->nxs);
-  ALLOC(b->home_P, sizeof(double) * (size_t)batch * b->n * b->ld);
+  DevOwner& own = b->own;
+  const size_t Bz = (size_t)batch, nz = (size_t)b->n;
+  int rc = own.alloc(&b->home_x, Bz * b->nxs);
+  if (!rc) rc = own.alloc(&b->home_P, Bz * nz * b->ld);
+  if (!rc) rc = own.alloc(&b->d_Qx, nz);
+  if (!rc) rc = own.alloc(&b->d_lambda, nz);
+  if (!rc) rc = own.alloc(&b->d_Pdiag, nz);
+  if (!rc) rc = own.alloc(&b->d_x0, 17);
+  if (!rc) rc = own.alloc(&b->d_ws, Bz * (size_t)b->ws_stride);
+  if (!rc) rc = own.alloc(&b->d_len, Bz);
+  if (!rc) rc = own.alloc(&b->d_flags, Bz);
+  if (!rc) rc = own.alloc(&b->d_dp, 1);
+  if (rc) {
+    viekf_batch_destroy(b);
+    return rc;
+  }
   point_live(b);
-  ALLOC(b->d_Qx, sizeof(double) * (size_t)b->n);
-  ALLOC(b->d_lambda, sizeof(double) * (size_t)b->n);
-  ALLOC(b->d_Pdiag, sizeof(double) * (size_t)b->n);
-  ALLOC(b->d_x0, sizeof(double) * 17);
-  ALLOC(b->d_ws, sizeof(double) * (size_t)batch * b->ws_stride);
-  ALLOC(b->d_len, sizeof(int) * (size_t)batch);
-  ALLOC(b->d_flags, sizeof(unsigned) * (size_t)batch);
-  ALLOC(b->d_dp, sizeof(DevParams));
-#undef ALLOC
   hipError_t e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
   if (e != hipSuccess) {
     viekf_batch_destroy(b);
@@ -164,7 +162,6 @@ int viekf_batch_create(int32_t batch, int32_t num_features, const viekf_params* 
       lam[16 + 3 * i + k] = p->lambda_feat[k];
       Pd[16 + 3 * i + k] = p->P0_feat[k];
     }
-  int rc = VIEKF_OK;
   auto up = [&](double* dptr, const double* h, size_t cnt) {
     if (hipMemcpy(dptr, h, cnt * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = VIEKF_ERR_HIP;
   };
@@ -189,11 +186,7 @@ int viekf_batch_destroy(viekf_batch* b) {
   if (!b) return VIEKF_OK;
   (void)hipSetDevice(b->device);
   if (b->stream) (void)hipStreamSynchronize(b->stream);
-  if (b->d_smap) (void)hipFree(b->d_smap);
-  if (b->d_zero) (void)hipFree(b->d_zero);
-  void* ptrs[] = {b->home_x, b->home_P, b->d_Qx, b->d_lambda, b->d_Pdiag, b->d_x0, b->d_ws, b->d_len, b->d_flags, b->d_stage, b->d_dp, b->h_x, b->h_P, b->h_len, b->d_active, b->d_ringslot, b->d_resmap, b->d_diag_ws};
-  for (void* q : ptrs)
-    if (q) (void)hipFree(q);
+  b->own.release_all();
   if (b->h_pin) (void)hipHostFree(b->h_pin);
   if (b->own_stream && b->stream) (void)hipStreamDestroy(b->stream);
   delete b;
@@ -679,14 +672,14 @@ int viekf_batch_history_resize(viekf_batch* b, int32_t depth) {
   }
   b->book.resized(0);
   point_live(b);
-  if (b->h_x) { HIP_TRY(hipFree(b->h_x)); b->h_x = nullptr; }
-  if (b->h_P) { HIP_TRY(hipFree(b->h_P)); b->h_P = nullptr; }
-  if (b->h_len) { HIP_TRY(hipFree(b->h_len)); b->h_len = nullptr; }
+  if (int rc = b->own.free(&b->h_x)) return rc;
+  if (int rc = b->own.free(&b->h_P)) return rc;
+  if (int rc = b->own.free(&b->h_len)) return rc;
   b->hist_depth = 0;
   if (depth == 0) return VIEKF_OK;
-  HIP_TRY(hipMalloc(&b->h_x, sizeof(double) * (size_t)depth * b->B * b->nxs));
-  HIP_TRY(hipMalloc(&b->h_P, sizeof(double) * (size_t)depth * b->B * b->n * b->ld));
-  HIP_TRY(hipMalloc(&b->h_len, sizeof(int) * (size_t)depth * b->B));
+  if (int rc = b->own.alloc(&b->h_x, (size_t)depth * b->B * b->nxs)) return rc;
+  if (int rc = b->own.alloc(&b->h_P, (size_t)depth * b->B * b->n * b->ld)) return rc;
+  if (int rc = b->own.alloc(&b->h_len, (size_t)depth * b->B)) return rc;
   b->hist_depth = depth;
   b->book.resized(depth);
   return VIEKF_OK;
@@ -716,7 +709,8 @@ int viekf_batch_set_active(viekf_batch* b, const uint8_t* mask, viekf_mem where)
   if (int rc = check_batch(b)) return rc;
   HIP_TRY(hipSetDevice(b->device));
   if (!mask) { b->active_on = false; return VIEKF_OK; }
-  if (!b->d_active) HIP_TRY(hipMalloc(&b->d_active, (size_t)b->B));
+  if (!b->d_active)
+    if (int rc = b->own.alloc(&b->d_active, (size_t)b->B)) return rc;
   const void* from = mask;
   if (where == VIEKF_HOST && b->async_host) {   // through the pinned ring: nothing to wait for (the mask itself stays a DEVICE copy:
     if (int rc = stage_begin(b, stage_size((size_t)b->B))) return rc;   // it outlives any number of launches)
@@ -747,7 +741,8 @@ static int ring_filters(viekf_batch* b, const int32_t* slot, viekf_mem where, in
   const int* d_slot = nullptr;
   Staged st(b, where);
   if (where == VIEKF_HOST && !b->async_host) {   // (a buffer of the batch's own, not the staging region)
-    if (!b->d_ringslot) HIP_TRY(hipMalloc(&b->d_ringslot, sizeof(int) * (size_t)b->B));
+    if (!b->d_ringslot)
+      if (int rc = b->own.alloc(&b->d_ringslot, (size_t)b->B)) return rc;
     HIP_TRY(hipMemcpyAsync(b->d_ringslot, slot, sizeof(int) * (size_t)b->B, hipMemcpyHostToDevice, b->stream));
     d_slot = b->d_ringslot;
   } else {   // (async: read by this one launch straight from the pinned ring, nothing to wait for)
@@ -840,7 +835,8 @@ int viekf_batch_select_filters(viekf_batch* b, const int32_t* slot) {
   HIP_TRY(hipSetDevice(b->device));
   if (int rc = canonicalize_all(b)) return rc;   // (per-filter live slots keep today's canonical path: every buffer first)
   if (!b->book.per_filter()) {
-    if (!b->d_smap) HIP_TRY(hipMalloc(&b->d_smap, sizeof(int) * (size_t)b->B));
+    if (!b->d_smap)
+      if (int rc = b->own.alloc(&b->d_smap, (size_t)b->B)) return rc;
     b->live_slots.assign((size_t)b->B, 0);
     b->book.enter_per_filter();
     point_live(b);
@@ -1011,484 +1007,9 @@ int viekf_batch_step_n(viekf_batch* b, int32_t K, const double* u, const double*
   return update_or_step(b, u, dt, true, z, slot, M, R, r_mode, result, where, K);
 }
 
-// ---- consistency diagnostics (include/viekf_diag.h, viekf_kernels_diag.hpp): read-only, the lower triangle of P only ----
-int viekf_diag_consistency(viekf_batch* b, const double* x_true, double* logdet, double* nees, double* whitened, int32_t* info,
-                           viekf_mem where) {
-  if (int rc = check_batch(b)) return rc;
-  if (!logdet && !nees && !whitened && !info) return fail(VIEKF_ERR_INVALID, "at least one output must not be null");
-  if (!x_true && (nees || whitened)) return fail(VIEKF_ERR_INVALID, "nees and whitened need x_true");
-  HIP_TRY(hipSetDevice(b->device));
-  if (int rc = require_P(b, PForm::Lower)) return rc;
-  const size_t B = (size_t)b->B;
-  const double* d_xt = nullptr;
-  double *d_ld = nullptr, *d_ne = nullptr, *d_wh = nullptr;
-  int32_t* d_info = nullptr;
-  Staged st(b, where);   // (four outputs; Staged keeps track of kMaxOut, viekf_staging.hpp)
-  if (int rc = st.begin(in(x_true, B * b->nx, &d_xt), out(logdet, B, &d_ld), out(nees, 4 * B, &d_ne), out(whitened, B * b->n, &d_wh),
-                        out(info, B, &d_info)))
-    return rc;
-  StreamArgs a = make_args(b);
-  const size_t lds = sizeof(double) * (size_t)diag_packed_doubles(b->n);
-  if (lds + 1024 <= 160 * 1024) {   // the packed triangle in LDS (N <= VIEKF_DIAG_ONCHIP_MAX_FEATURES; + the kernel's static LDS)
-    static size_t have[64] = {};
-    if (int rc = raise_dyn_lds({&k_diag_consistency<DG_T, true>}, lds, have[b->device & 63])) return rc;
-    hipLaunchKernelGGL((k_diag_consistency<DG_T, true>), dim3(b->B), dim3(DG_T), lds, b->stream, a, 0, d_xt, nullptr, 0L, d_ld, d_ne,
-                       d_wh, d_info);
-    HIP_TRY(hipGetLastError());
-  } else {                          // the same algorithm on a copy in the batch's workspace, a chunk of filters per launch
-    const size_t stride = ((size_t)diag_packed_doubles(b->n) + 1) & ~size_t(1), per = sizeof(double) * stride;
-    const size_t chunk = std::min(B, std::max<size_t>(1, (size_t(256) << 20) / per));
-    if (chunk * per > b->diag_ws_bytes) {
-      HIP_TRY(hipStreamSynchronize(b->stream));
-      if (b->d_diag_ws) HIP_TRY(hipFree(b->d_diag_ws));
-      b->d_diag_ws = nullptr; b->diag_ws_bytes = 0;
-      HIP_TRY(hipMalloc(&b->d_diag_ws, chunk * per));
-      b->diag_ws_bytes = chunk * per;
-    }
-    for (size_t b0 = 0; b0 < B; b0 += chunk) {   // (launches of one stream: the next chunk reuses the workspace after this one)
-      hipLaunchKernelGGL((k_diag_consistency<DG_T, false>), dim3((unsigned)std::min(chunk, B - b0)), dim3(DG_T), 0, b->stream, a, (int)b0,
-                         d_xt, b->d_diag_ws, (long)stride, d_ld, d_ne, d_wh, d_info);
-      HIP_TRY(hipGetLastError());
-    }
-  }
-  return st.finish();
-}
-
-int viekf_diag_innovation(viekf_batch* b, int32_t type, int32_t M, const double* z, int32_t zdim, const int32_t* slot, const double* R,
-                          int32_t rdim, int32_t r_mode, double* nis, double* residual, double* S, viekf_mem where) {
-  if (int rc = check_batch(b)) return rc;
-  if (!z || !R || !nis) return fail(VIEKF_ERR_INVALID, "z, R and nis must not be null");
-  if (type < 0 || type >= VIEKF_TOTAL_MEAS || type == VIEKF_PIXEL_VEL)
-    return fail(VIEKF_ERR_UNSUPPORTED, "measurement type not supported (PIXEL_VEL is an empty TODO in the reference)");
-  if (zdim < 1 || zdim > 4 || rdim < 1 || rdim > 3 || r_mode < 0 || r_mode > 2)
-    return fail(VIEKF_ERR_INVALID, "need 1 <= zdim <= 4, 1 <= rdim <= 3, r_mode 0, 1 or 2");
-  if ((type == VIEKF_ATT || type == VIEKF_QZETA) && zdim != 4) return fail(VIEKF_ERR_INVALID, "ATT and QZETA take a quaternion: zdim 4");
-  const bool needs_slot = type == VIEKF_QZETA || type == VIEKF_FEAT || type == VIEKF_DEPTH || type == VIEKF_INV_DEPTH;
-  if (M < 1) return fail(VIEKF_ERR_INVALID, "M must be >= 1");
-  if (needs_slot && !slot) return fail(VIEKF_ERR_INVALID, "slot must not be null for feature measurements");
-  if (!needs_slot && (M != 1 || slot)) return fail(VIEKF_ERR_INVALID, "this measurement model takes M == 1 and no slot");
-  HIP_TRY(hipSetDevice(b->device));
-  if (int rc = require_P(b, PForm::Lower)) return rc;
-  const size_t BM = (size_t)b->B * (size_t)M, rr = (size_t)rdim * rdim;
-  const double *d_z = nullptr, *d_R = nullptr;
-  const int32_t* d_slot = nullptr;
-  double *d_nis = nullptr, *d_res = nullptr, *d_S = nullptr;
-  Staged st(b, where);
-  if (int rc = st.begin(in(z, BM * zdim, &d_z), in(slot, BM, &d_slot), in(R, r_mode == 0 ? rr : (r_mode == 1 ? rr * b->B : rr * BM), &d_R),
-                        out(nis, BM, &d_nis), out(residual, 3 * BM, &d_res), out(S, 9 * BM, &d_S)))
-    return rc;
-  StreamArgs a = make_args(b);
-  const long rsb = r_mode == 1 ? (long)rr : (r_mode == 2 ? (long)rr * M : 0L), rsm = r_mode == 2 ? (long)rr : 0L;
-  hipLaunchKernelGGL(k_diag_innovation, dim3((unsigned)((BM + 63) / 64)), dim3(64), 0, b->stream, a, type, M, d_z, zdim, d_slot, d_R,
-                     rdim, rsb, rsm, d_nis, d_res, d_S);
-  HIP_TRY(hipGetLastError());
-  return st.finish();
-}
-
 }  // extern "C"
 
-// ---- device-resident frame intake (include/viekf_frame.h, viekf_kernels_frame.hpp) ----
-struct viekf_frame {
-  viekf_batch* b = nullptr;
-  int device = 0;
-  FrameTabs t = {};
-  int mcap = 0;   // capacity of the M-sized rows (grown when a frame is longer; they are addressed with the call's own M)
-};
-
-namespace {
-
-int check_frame(const viekf_frame* f) {
-  if (!f || !f->b) return fail(VIEKF_ERR_INVALID, "null frame intake handle");
-  return VIEKF_OK;
-}
-
-template <typename T>
-int frame_alloc(T** p, size_t count) {
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(p), sizeof(T) * std::max<size_t>(count, 1)));
-  return VIEKF_OK;
-}
-
-// rows for frames of up to M entries: the per-frame arrays are simply replaced, the keyframe lists move into wider rows
-int frame_reserve(viekf_frame* f, int M) {
-  if (M <= f->mcap) return VIEKF_OK;
-  viekf_batch* b = f->b;
-  FrameTabs& t = f->t;
-  const size_t B = (size_t)b->B;
-  const int cap = std::max(64, std::max(M, b->N));
-  HIP_TRY(hipStreamSynchronize(b->stream));
-  void* old[] = {t.code, t.pos, t.slot_u, t.z_u, t.R_u, t.res_u};
-  for (void* q : old)
-    if (q) HIP_TRY(hipFree(q));
-  t.code = t.pos = t.slot_u = t.res_u = nullptr; t.z_u = t.R_u = nullptr;
-  f->mcap = 0;
-  if (int rc = frame_alloc(&t.code, B * cap)) return rc;
-  if (int rc = frame_alloc(&t.pos, B * cap)) return rc;
-  if (int rc = frame_alloc(&t.slot_u, B * cap)) return rc;
-  if (int rc = frame_alloc(&t.res_u, B * cap)) return rc;
-  if (int rc = frame_alloc(&t.z_u, 2 * B * cap)) return rc;
-  if (int rc = frame_alloc(&t.R_u, 4 * B * cap)) return rc;
-  int* kf = nullptr;
-  if (int rc = frame_alloc(&kf, B * cap)) return rc;
-  hipError_t e = hipMemset(kf, 0xff, sizeof(int) * B * cap);
-  if (e == hipSuccess && t.kf)
-    e = hipMemcpy2D(kf, sizeof(int) * cap, t.kf, sizeof(int) * t.kfcap, sizeof(int) * t.kfcap, B, hipMemcpyDeviceToDevice);
-  if (e != hipSuccess) { (void)hipFree(kf); return fail(VIEKF_ERR_HIP, std::string("keyframe list move failed: ") + hipGetErrorString(e)); }
-  if (t.kf) HIP_TRY(hipFree(t.kf));
-  t.kf = kf; t.kfcap = cap;
-  f->mcap = cap;
-  return VIEKF_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int viekf_frame_destroy(viekf_frame* f) {
-  if (!f) return fail(VIEKF_ERR_INVALID, "null frame intake handle");
-  (void)hipSetDevice(f->device);
-  (void)hipDeviceSynchronize();   // (not the batch's stream: the tables may be freed after their batch is gone)
-  FrameTabs& t = f->t;
-  void* ptrs[] = {t.tab, t.tlen, t.kf, t.kflen, t.keep, t.rmask, t.newcnt, t.newpix, t.newdepth, t.code, t.pos, t.slot_u, t.z_u, t.R_u, t.res_u};
-  for (void* q : ptrs)
-    if (q) (void)hipFree(q);
-  delete f;
-  return VIEKF_OK;
-}
-
-int viekf_frame_create(viekf_batch* b, viekf_frame** out) {
-  if (!out) return fail(VIEKF_ERR_INVALID, "null argument");
-  *out = nullptr;
-  if (int rc = check_batch(b)) return rc;
-  HIP_TRY(hipSetDevice(b->device));
-  viekf_frame* f = new viekf_frame();
-  f->b = b; f->device = b->device;
-  FrameTabs& t = f->t;
-  const size_t B = (size_t)b->B, BN = B * (size_t)b->N;
-  int rc = frame_alloc(&t.tab, BN);
-  if (!rc) rc = frame_alloc(&t.tlen, B);
-  if (!rc) rc = frame_alloc(&t.kflen, B);
-  if (!rc) rc = frame_alloc(&t.keep, BN);
-  if (!rc) rc = frame_alloc(&t.rmask, B);
-  if (!rc) rc = frame_alloc(&t.newcnt, B);
-  if (!rc) rc = frame_alloc(&t.newpix, 2 * BN);
-  if (!rc) rc = frame_alloc(&t.newdepth, BN);
-  if (!rc) rc = frame_reserve(f, std::max(64, b->N));
-  if (!rc) rc = viekf_frame_reset(f);
-  if (rc) { viekf_frame_destroy(f); return rc; }
-  *out = f;
-  return VIEKF_OK;
-}
-
-int viekf_frame_reset(viekf_frame* f) {
-  if (int rc = check_frame(f)) return rc;
-  viekf_batch* b = f->b;
-  HIP_TRY(hipSetDevice(b->device));
-  const size_t B = (size_t)b->B;
-  HIP_TRY(hipMemsetAsync(f->t.tab, 0xff, sizeof(int) * std::max<size_t>(B * b->N, 1), b->stream));   // (-1)
-  HIP_TRY(hipMemsetAsync(f->t.tlen, 0, sizeof(int) * B, b->stream));
-  HIP_TRY(hipMemsetAsync(f->t.kflen, 0, sizeof(int) * B, b->stream));
-  HIP_TRY(hipStreamSynchronize(b->stream));
-  return VIEKF_OK;
-}
-
-int viekf_frame_set_tracked(viekf_frame* f, const int32_t* ids, viekf_mem where) {
-  if (int rc = check_frame(f)) return rc;
-  if (!ids) return fail(VIEKF_ERR_INVALID, "ids is null");
-  if (where != VIEKF_HOST && where != VIEKF_DEVICE) return fail(VIEKF_ERR_INVALID, "where must be VIEKF_HOST or VIEKF_DEVICE");
-  viekf_batch* b = f->b;
-  HIP_TRY(hipSetDevice(b->device));
-  const int B = b->B, N = b->N;
-  if (where == VIEKF_HOST) {   // row b: len_features[b] distinct ids >= 0, then -1
-    std::vector<int32_t> len((size_t)B);
-    HIP_TRY(hipMemcpyAsync(len.data(), b->d_len, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    for (int i = 0; i < B; i++) {
-      const int32_t* row = ids + (size_t)i * N;
-      for (int k = 0; k < N; k++) {
-        if (k < len[(size_t)i] ? row[k] < 0 : row[k] != -1)
-          return fail(VIEKF_ERR_INVALID, "set_tracked: a row must hold len_features ids >= 0, then -1 (wrong length)");
-        for (int j = 0; k < len[(size_t)i] && j < k; j++)
-          if (row[j] == row[k]) return fail(VIEKF_ERR_INVALID, "set_tracked: duplicate id in a row");
-      }
-    }
-  }
-  HIP_TRY(hipMemcpyAsync(f->t.tab, ids, sizeof(int32_t) * (size_t)B * N, where == VIEKF_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
-                         b->stream));
-  hipLaunchKernelGGL(k_frame_adopt, dim3(B), dim3(64), 0, b->stream, B, N, f->t.tab, f->t.tlen);
-  HIP_TRY(hipGetLastError());
-  if (where == VIEKF_HOST) HIP_TRY(hipStreamSynchronize(b->stream));
-  return VIEKF_OK;
-}
-
-int viekf_frame_tracked(viekf_frame* f, int32_t* ids, int32_t* len, viekf_mem where) {
-  if (int rc = check_frame(f)) return rc;
-  if (where != VIEKF_HOST && where != VIEKF_DEVICE) return fail(VIEKF_ERR_INVALID, "where must be VIEKF_HOST or VIEKF_DEVICE");
-  viekf_batch* b = f->b;
-  HIP_TRY(hipSetDevice(b->device));
-  const hipMemcpyKind kind = where == VIEKF_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-  if (ids && b->N > 0) HIP_TRY(hipMemcpyAsync(ids, f->t.tab, sizeof(int32_t) * (size_t)b->B * b->N, kind, b->stream));
-  if (len) HIP_TRY(hipMemcpyAsync(len, f->t.tlen, sizeof(int32_t) * (size_t)b->B, kind, b->stream));
-  if (where == VIEKF_HOST) HIP_TRY(hipStreamSynchronize(b->stream));
-  return VIEKF_OK;
-}
-
-// plan -> k_keep_features -> k_keyframe_reset -> k_init_features -> the batch's FEAT update -> finish, all on the batch's
-// stream and nothing of it waited for; the host never learns how many features a filter dropped or started.
-int viekf_frame_intake(viekf_frame* f, int32_t M, const double* z, const int32_t* ids, const double* depth, const double* R,
-                       int32_t r_mode, const uint8_t* active, int32_t* result, int32_t* gated, int32_t* gated_count,
-                       uint8_t* did_reset, double* edges, viekf_mem where) {
-  if (int rc = check_frame(f)) return rc;
-  viekf_batch* b = f->b;
-  if (M < 1 || M > VIEKF_FRAME_MAX_M) return fail(VIEKF_ERR_INVALID, "need 1 <= M <= 4096 entries per frame");
-  if (!z || !ids || !R) return fail(VIEKF_ERR_INVALID, "z, ids and R must not be null");
-  if (r_mode < 0 || r_mode > 2) return fail(VIEKF_ERR_INVALID, "r_mode must be 0, 1 or 2");
-  if (where != VIEKF_HOST && where != VIEKF_DEVICE) return fail(VIEKF_ERR_INVALID, "where must be VIEKF_HOST or VIEKF_DEVICE");
-  if (b->active_on)
-    return fail(VIEKF_ERR_INVALID, "viekf_frame_intake under a participation mask (viekf_batch_set_active(NULL) first; the call takes its own `active`)");
-  HIP_TRY(hipSetDevice(b->device));
-  if (int rc = frame_reserve(f, M)) return rc;
-  // keep and reset read and write all of P; the host cannot know whether either will have anything to do
-  if (int rc = require_P(b, PForm::Full)) return rc;
-  const size_t B = (size_t)b->B, BM = B * (size_t)M;
-  const double *d_z = nullptr, *d_depth = nullptr, *d_R = nullptr;
-  const int32_t* d_ids = nullptr;
-  const uint8_t* d_act = nullptr;
-  int32_t *d_res = nullptr, *d_gated = nullptr, *d_gc = nullptr;
-  uint8_t* d_dr = nullptr;
-  double* d_edges = nullptr;
-  Staged st(b, where);
-  if (int rc = st.begin(in(z, 2 * BM, &d_z), in(ids, BM, &d_ids), in(depth, BM, &d_depth), in(R, r_count(b, M, r_mode), &d_R),
-                        in(active, B, &d_act), out(result, BM, &d_res), out(gated, BM, &d_gated), out(gated_count, B, &d_gc),
-                        out(did_reset, B, &d_dr), out(edges, 17 * B, &d_edges)))
-    return rc;
-  const FrameTabs& t = f->t;
-  StreamArgs a = make_args(b);
-  const int use_kfr = b->params.use_keyframe_reset != 0;
-  const size_t plds = sizeof(int) * (2 * (size_t)M + 2 * (size_t)b->N);
-  hipLaunchKernelGGL(k_frame_plan, dim3(b->B), dim3(64), plds, b->stream, a, t, M, d_z, d_ids, d_depth, d_R, r_mode, d_act, use_kfr,
-                     b->params.keyframe_overlap_threshold, d_edges);
-  HIP_TRY(hipGetLastError());
-  const size_t klds = sizeof(double) * (size_t)b->n + sizeof(int) * (size_t)(b->n + 4);
-  hipLaunchKernelGGL(k_keep_features<kThreads>, dim3(b->B), dim3(kThreads), klds, b->stream, a, t.keep, nullptr);
-  HIP_TRY(hipGetLastError());
-  if (use_kfr) {
-    hipLaunchKernelGGL(k_keyframe_reset<kThreads>, dim3(b->B), dim3(kThreads), 0, b->stream, a, t.rmask, d_edges);
-    HIP_TRY(hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_init_features<kThreads>, dim3(b->B), dim3(kThreads), 0, b->stream, a, t.newcnt, t.newpix, t.newdepth);
-  HIP_TRY(hipGetLastError());
-  const double* Ru = r_mode == 2 ? t.R_u : d_R;
-  if (use_resident(b)) {
-    if (int rc = launch_resident(b, false, nullptr, nullptr, t.z_u, t.slot_u, M, Ru, r_mode, t.res_u)) return rc;
-  } else {
-    if (int rc = launch_update(b, t.z_u, t.slot_u, M, Ru, r_mode, t.res_u)) return rc;
-  }
-  hipLaunchKernelGGL(k_frame_finish, dim3(b->B), dim3(64), 0, b->stream, b->B, t, M, d_ids, d_res, d_gated, d_gc, d_dr);
-  HIP_TRY(hipGetLastError());
-  return st.finish();
-}
-
-}  // extern "C"
-
-// ---- device-resident node graph (include/viekf_node.h, viekf_kernels_node.hpp) ----
-struct viekf_node {
-  viekf_batch* b = nullptr;
-  int device = 0;
-  NodeTabs t = {};
-};
-
-namespace {
-
-int check_node(const viekf_node* nd) {
-  if (!nd || !nd->b) return fail(VIEKF_ERR_INVALID, "null node graph handle");
-  return VIEKF_OK;
-}
-
-int check_where(viekf_mem where) {
-  if (where != VIEKF_HOST && where != VIEKF_DEVICE) return fail(VIEKF_ERR_INVALID, "where must be VIEKF_HOST or VIEKF_DEVICE");
-  return VIEKF_OK;
-}
-
-// Where the 21 elements of P that viekf_node_global reads lie IN THE FORM THE LIVE P IS IN (the book's, viekf_pform.hpp):
-// canonical (Full or Lower: the lower triangle is current in both) row + column * ld, or the body block of the packed image of
-// the batch's instance (ResPack, viekf_instance_rows.hpp -- the rows viekf_debug_packed_layout reports).
-NodeOffs node_offsets(const viekf_batch* b) {
-  const int idx[6] = {dxPOS, dxPOS + 1, dxPOS + 2, dxATT, dxATT + 1, dxATT + 2};
-  NodeOffs of;
-  if (b->book.live_form() == PForm::Packed) {   // (only ever left by the batch's instance of the resident family)
-    const ResInst& r = kResInst[b->res_inst];
-    const ResPack K(b->N, r.RB, r.NW);
-    for (int i = 0; i < 6; i++)
-      for (int j = 0; j <= i; j++) of.o[i * (i + 1) / 2 + j] = K.body(idx[i], idx[j]);
-  } else {
-    for (int i = 0; i < 6; i++)
-      for (int j = 0; j <= i; j++) of.o[i * (i + 1) / 2 + j] = idx[i] + idx[j] * b->ld;
-  }
-  return of;
-}
-
-unsigned node_grid(const viekf_batch* b) { return (unsigned)((b->B + 63) / 64); }
-
-}  // namespace
-
-extern "C" {
-
-int viekf_node_destroy(viekf_node* nd) {
-  if (!nd) return fail(VIEKF_ERR_INVALID, "null node graph handle");
-  (void)hipSetDevice(nd->device);
-  (void)hipDeviceSynchronize();   // (not the batch's stream: the tables may be freed after their batch is gone)
-  NodeTabs& t = nd->t;
-  void* ptrs[] = {t.node, t.cov, t.tnode, t.count, t.tr_node, t.tr_edge};
-  for (void* q : ptrs)
-    if (q) (void)hipFree(q);
-  delete nd;
-  return VIEKF_OK;
-}
-
-int viekf_node_create(viekf_batch* b, int32_t trail_capacity, viekf_node** out) {
-  if (!out) return fail(VIEKF_ERR_INVALID, "null argument");
-  *out = nullptr;
-  if (int rc = check_batch(b)) return rc;
-  if (trail_capacity < 0 || trail_capacity > VIEKF_NODE_MAX_TRAIL) return fail(VIEKF_ERR_INVALID, "need 0 <= trail_capacity <= 4096");
-  HIP_TRY(hipSetDevice(b->device));
-  viekf_node* nd = new viekf_node();
-  nd->b = b; nd->device = b->device;
-  NodeTabs& t = nd->t;
-  t.cap = trail_capacity;
-  const size_t B = (size_t)b->B;
-  int rc = frame_alloc(&t.node, 7 * B);
-  if (!rc) rc = frame_alloc(&t.cov, 36 * B);
-  if (!rc) rc = frame_alloc(&t.tnode, 7 * B);
-  if (!rc) rc = frame_alloc(&t.count, B);
-  if (!rc) rc = frame_alloc(&t.tr_node, 7 * B * (size_t)t.cap);
-  if (!rc) rc = frame_alloc(&t.tr_edge, 17 * B * (size_t)t.cap);
-  if (!rc) rc = viekf_node_reset(nd);
-  if (rc) { viekf_node_destroy(nd); return rc; }
-  *out = nd;
-  return VIEKF_OK;
-}
-
-int viekf_node_reset(viekf_node* nd) {
-  if (int rc = check_node(nd)) return rc;
-  viekf_batch* b = nd->b;
-  HIP_TRY(hipSetDevice(b->device));
-  const NodeTabs& t = nd->t;
-  hipLaunchKernelGGL(k_node_reset, dim3(node_grid(b)), dim3(64), 0, b->stream, b->B, t);
-  HIP_TRY(hipGetLastError());
-  if (t.cap > 0) {
-    HIP_TRY(hipMemsetAsync(t.tr_node, 0, sizeof(double) * 7 * (size_t)b->B * t.cap, b->stream));
-    HIP_TRY(hipMemsetAsync(t.tr_edge, 0, sizeof(double) * 17 * (size_t)b->B * t.cap, b->stream));
-  }
-  HIP_TRY(hipStreamSynchronize(b->stream));
-  return VIEKF_OK;
-}
-
-int viekf_node_update(viekf_node* nd, const uint8_t* did_reset, const double* edges, const double* x_true, int32_t ldx, viekf_mem where) {
-  if (int rc = check_node(nd)) return rc;
-  if (!did_reset || !edges) return fail(VIEKF_ERR_INVALID, "did_reset and edges must not be null");
-  if (x_true && ldx < 10) return fail(VIEKF_ERR_INVALID, "x_true needs ldx >= 10 (position 0:3, attitude 6:10)");
-  if (int rc = check_where(where)) return rc;
-  viekf_batch* b = nd->b;
-  HIP_TRY(hipSetDevice(b->device));
-  const size_t B = (size_t)b->B;
-  const uint8_t* d_dr = nullptr;
-  const double *d_e = nullptr, *d_xt = nullptr;
-  Staged st(b, where);
-  if (int rc = st.begin(in(did_reset, B, &d_dr), in(edges, 17 * B, &d_e), in(x_true, x_true ? B * (size_t)ldx : 0, &d_xt))) return rc;
-  hipLaunchKernelGGL(k_node_update, dim3(node_grid(b)), dim3(64), 0, b->stream, b->B, nd->t, d_dr, d_e, d_xt, ldx);
-  HIP_TRY(hipGetLastError());
-  return st.finish();
-}
-
-// read-only, and P is read in the form it is in: no require_P here (an unpack would cross all of P to read 21 numbers)
-int viekf_node_global(viekf_node* nd, double* pose, double* cov, viekf_mem where) {
-  if (int rc = check_node(nd)) return rc;
-  if (!pose && !cov) return fail(VIEKF_ERR_INVALID, "at least one output must not be null");
-  if (int rc = check_where(where)) return rc;
-  viekf_batch* b = nd->b;
-  HIP_TRY(hipSetDevice(b->device));
-  const size_t B = (size_t)b->B;
-  double *d_pose = nullptr, *d_cov = nullptr;
-  Staged st(b, where);
-  if (int rc = st.begin(out(pose, 7 * B, &d_pose), out(cov, 36 * B, &d_cov))) return rc;
-  hipLaunchKernelGGL(k_node_global, dim3(node_grid(b)), dim3(64), 0, b->stream, make_args(b), nd->t, node_offsets(b), d_pose, d_cov);
-  HIP_TRY(hipGetLastError());
-  return st.finish();
-}
-
-int viekf_node_relative_truth(viekf_node* nd, const double* x_true, double* x_rel, int32_t ldx, viekf_mem where) {
-  if (int rc = check_node(nd)) return rc;
-  if (!x_true || !x_rel) return fail(VIEKF_ERR_INVALID, "x_true and x_rel must not be null");
-  if (ldx < 10) return fail(VIEKF_ERR_INVALID, "x_true needs ldx >= 10 (position 0:3, attitude 6:10)");
-  if (int rc = check_where(where)) return rc;
-  viekf_batch* b = nd->b;
-  HIP_TRY(hipSetDevice(b->device));
-  const size_t cnt = (size_t)b->B * (size_t)ldx;
-  const double* d_xt = nullptr;
-  double* d_xr = nullptr;
-  Staged st(b, where);
-  if (int rc = st.begin(in(x_true, cnt, &d_xt), out(x_rel, cnt, &d_xr))) return rc;
-  hipLaunchKernelGGL(k_node_relative_truth, dim3(b->B), dim3(64), 0, b->stream, b->B, nd->t, d_xt, d_xr, ldx);
-  HIP_TRY(hipGetLastError());
-  return st.finish();
-}
-
-int viekf_node_global_error(viekf_node* nd, const double* x_true, int32_t ldx, double* err, double* nees, int32_t* info, viekf_mem where) {
-  if (int rc = check_node(nd)) return rc;
-  if (!x_true) return fail(VIEKF_ERR_INVALID, "x_true must not be null");
-  if (!err && !nees && !info) return fail(VIEKF_ERR_INVALID, "at least one output must not be null");
-  if (ldx < 10) return fail(VIEKF_ERR_INVALID, "x_true needs ldx >= 10 (position 0:3, attitude 6:10)");
-  if (int rc = check_where(where)) return rc;
-  viekf_batch* b = nd->b;
-  HIP_TRY(hipSetDevice(b->device));
-  const size_t B = (size_t)b->B;
-  const double* d_xt = nullptr;
-  double *d_err = nullptr, *d_nees = nullptr;
-  int32_t* d_info = nullptr;
-  Staged st(b, where);
-  if (int rc = st.begin(in(x_true, B * (size_t)ldx, &d_xt), out(err, 6 * B, &d_err), out(nees, B, &d_nees), out(info, B, &d_info))) return rc;
-  hipLaunchKernelGGL(k_node_global_error, dim3(node_grid(b)), dim3(64), 0, b->stream, make_args(b), nd->t, node_offsets(b), d_xt, ldx,
-                     d_err, d_nees, d_info);
-  HIP_TRY(hipGetLastError());
-  return st.finish();
-}
-
-static int node_copy(viekf_node* nd, bool get, void* node, void* node_cov, void* true_node, void* count, viekf_mem where) {
-  if (int rc = check_node(nd)) return rc;
-  if (int rc = check_where(where)) return rc;
-  viekf_batch* b = nd->b;
-  HIP_TRY(hipSetDevice(b->device));
-  const hipMemcpyKind kind = where == VIEKF_DEVICE ? hipMemcpyDeviceToDevice : (get ? hipMemcpyDeviceToHost : hipMemcpyHostToDevice);
-  const size_t B = (size_t)b->B;
-  const NodeTabs& t = nd->t;
-  struct Arr { void* user; void* dev; size_t bytes; } arrs[] = {{node, t.node, sizeof(double) * 7 * B}, {node_cov, t.cov, sizeof(double) * 36 * B},
-                                                                {true_node, t.tnode, sizeof(double) * 7 * B}, {count, t.count, sizeof(int32_t) * B}};
-  for (const Arr& a : arrs)
-    if (a.user) HIP_TRY(hipMemcpyAsync(get ? a.user : a.dev, get ? a.dev : a.user, a.bytes, kind, b->stream));
-  if (where == VIEKF_HOST) HIP_TRY(hipStreamSynchronize(b->stream));
-  return VIEKF_OK;
-}
-
-int viekf_node_get(viekf_node* nd, double* node, double* node_cov, double* true_node, int32_t* count, viekf_mem where) {
-  return node_copy(nd, true, node, node_cov, true_node, count, where);
-}
-
-int viekf_node_set(viekf_node* nd, const double* node, const double* node_cov, const double* true_node, const int32_t* count, viekf_mem where) {
-  return node_copy(nd, false, const_cast<double*>(node), const_cast<double*>(node_cov), const_cast<double*>(true_node),
-                   const_cast<int32_t*>(count), where);
-}
-
-int viekf_node_trail(viekf_node* nd, double* nodes, double* edges, viekf_mem where) {
-  if (int rc = check_node(nd)) return rc;
-  if (int rc = check_where(where)) return rc;
-  viekf_batch* b = nd->b;
-  HIP_TRY(hipSetDevice(b->device));
-  const hipMemcpyKind kind = where == VIEKF_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-  const size_t rows = (size_t)b->B * (size_t)nd->t.cap;
-  if (nodes && rows) HIP_TRY(hipMemcpyAsync(nodes, nd->t.tr_node, sizeof(double) * 7 * rows, kind, b->stream));
-  if (edges && rows) HIP_TRY(hipMemcpyAsync(edges, nd->t.tr_edge, sizeof(double) * 17 * rows, kind, b->stream));
-  if (where == VIEKF_HOST) HIP_TRY(hipStreamSynchronize(b->stream));
-  return VIEKF_OK;
-}
-
-}  // extern "C"
+// the companions of a batch, each with its handle and helpers (still this one translation unit)
+#include "viekf_capi_diag.hpp"
+#include "viekf_capi_frame.hpp"
+#include "viekf_capi_node.hpp"

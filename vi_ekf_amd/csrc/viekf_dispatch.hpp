@@ -38,8 +38,9 @@ int raise_dyn_lds(std::initializer_list<Kernel*> kernels, size_t bytes, size_t& 
 }
 
 // elements and strides of the measurement noise R: r_mode 0 one R for all, 1 one per filter, 2 one per filter and measurement
-size_t r_count(const viekf_batch* b, int M, int r_mode) {
-  return r_mode == 0 ? 4 : (r_mode == 1 ? 4 * (size_t)b->B : 4 * (size_t)b->B * M);
+// (rr elements each: the 2 x 2 of a pixel measurement unless the caller has another rdim)
+size_t r_count(const viekf_batch* b, int M, int r_mode, size_t rr = 4) {
+  return r_mode == 0 ? rr : (r_mode == 1 ? rr * (size_t)b->B : rr * (size_t)b->B * M);
 }
 void r_strides(int r_mode, int M, long* rsb, long* rsm) {
   *rsb = r_mode == 1 ? 4 : (r_mode == 2 ? 4L * M : 0);
@@ -260,8 +261,8 @@ int setup_resident(viekf_batch* b) {
     }
     std::vector<int> map;
     if (!build_resmap(b->N, r.RB, r.NW, map)) continue;
-    if (b->d_resmap) { HIP_TRY(hipFree(b->d_resmap)); b->d_resmap = nullptr; }
-    HIP_TRY(hipMalloc(&b->d_resmap, sizeof(int) * map.size()));
+    if (int rc = b->own.free(&b->d_resmap)) return rc;
+    if (int rc = b->own.alloc(&b->d_resmap, map.size())) return rc;
     HIP_TRY(hipMemcpy(b->d_resmap, map.data(), sizeof(int) * map.size(), hipMemcpyHostToDevice));
     static size_t have[64][kNumResInst] = {};
     const res_kernel_t* k = kResKernels[i].k;
@@ -338,10 +339,8 @@ int launch_resident(viekf_batch* b, bool do_prop, const double* d_u, const doubl
 
 // per-filter mode: (x, P) of every filter between its live ring slot and the batch's own buffers (to_home != 0: ring -> home)
 int gather_scatter_home(viekf_batch* b, int to_home) {
-  if (!b->d_zero) {
-    HIP_TRY(hipMalloc(&b->d_zero, sizeof(int) * (size_t)b->B));
-    HIP_TRY(hipMemsetAsync(b->d_zero, 0, sizeof(int) * (size_t)b->B, b->stream));
-  }
+  if (!b->d_zero)
+    if (int rc = b->own.alloc_zeroed(&b->d_zero, (size_t)b->B, b->stream)) return rc;
   StreamArgs a = make_args(b);
   hipLaunchKernelGGL(k_ring_copy, dim3(b->B), dim3(256), 0, b->stream, a, b->home_x, b->home_P, b->d_zero, to_home, 1);
   HIP_TRY(hipGetLastError());

@@ -18,10 +18,9 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
-#include <string>
 
 #include "../../include/viekf_klt.h"
-#include "viekf_host.hpp"
+#include "viekf_hostkit.hpp"
 
 #pragma clang fp contract(off)
 
@@ -599,15 +598,6 @@ __global__ void k_get_level(KltDev k, int l, uint8_t* out) {
   if (p < n) out[(long long)b * n + p] = level_ptr(k, k.par[b], b, l)[p];
 }
 
-int fail(int code, const std::string& msg) { return viekf::set_last_error(code, msg); }
-
-#define HIP_TRY(expr)                                                                                  \
-  do {                                                                                                 \
-    hipError_t e_ = (expr);                                                                            \
-    if (e_ != hipSuccess)                                                                              \
-      return fail(VIEKF_ERR_HIP, std::string(#expr) + " failed: " + hipGetErrorString(e_));            \
-  } while (0)
-
 }  // namespace
 
 struct viekf_klt {
@@ -615,31 +605,19 @@ struct viekf_klt {
   int device = 0;
   hipStream_t stream = nullptr;
   bool own_stream = false;
+  DevOwner own;                         // every device buffer of d and below
   uint8_t* img = nullptr;               // staging of host frames [B][H][W][3]
   float* dimg = nullptr;                // staging of host depth images [B][H][W]
   double* depth = nullptr;              // [B][MF]
-  void* bufs[24] = {};
-  int nbufs = 0;
 };
 
 namespace {
 
-template <class T>
-int klt_alloc(viekf_klt* k, T** p, size_t bytes) {
-  void* q = nullptr;
-  HIP_TRY(hipMalloc(&q, bytes ? bytes : 1));
-  HIP_TRY(hipMemsetAsync(q, 0, bytes ? bytes : 1, k->stream));
-  k->bufs[k->nbufs++] = q;
-  *p = static_cast<T*>(q);
-  return VIEKF_OK;
-}
-
-void klt_free(viekf_klt* k) {
-  for (int i = 0; i < k->nbufs; i++) (void)hipFree(k->bufs[i]);
-  k->nbufs = 0;
-  if (k->img) (void)hipFree(k->img);
-  if (k->dimg) (void)hipFree(k->dimg);
+// the end of a tracker (the caller has set the device and waited for its stream)
+void klt_delete(viekf_klt* k) {
+  k->own.release_all();
   if (k->own_stream && k->stream) (void)hipStreamDestroy(k->stream);
+  delete k;
 }
 
 // the padded outputs of a camera that has not run a frame: NaN, -1, 0
@@ -652,9 +630,7 @@ int klt_clear_outputs(viekf_klt* k) {
 }
 
 int copy_out(viekf_klt* k, void* dst, const void* src, size_t bytes, viekf_mem where) {
-  if (!dst) return VIEKF_OK;
-  HIP_TRY(hipMemcpyAsync(dst, src, bytes, where == VIEKF_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, k->stream));
-  return VIEKF_OK;
+  return copy_user(dst, src, bytes, where, Copy::ToUser, k->stream);
 }
 
 int set_dev(const viekf_klt* k) {
@@ -697,18 +673,19 @@ int viekf_klt_create(int32_t batch, int32_t width, int32_t height, int32_t max_f
   d.pyr_sz = off;
   d.ccap = (long long)(width - 2) * (height - 2);
   int rc = VIEKF_OK;
-  auto fin = [&](int code) { klt_free(k); delete k; return code; };
+  auto fin = [&](int code) { klt_delete(k); return code; };
   if (hipStreamCreateWithFlags(&k->stream, hipStreamNonBlocking) != hipSuccess) return fin(fail(VIEKF_ERR_HIP, "hipStreamCreate failed"));
   k->own_stream = true;
   const long long B = batch, MF = max_features;
-  if ((rc = klt_alloc(k, &d.pyr, 2 * B * d.pyr_sz)) || (rc = klt_alloc(k, &d.par, 4 * B)) ||
-      (rc = klt_alloc(k, &d.mask, B * width * height)) || (rc = klt_alloc(k, &d.active, B)) ||
-      (rc = klt_alloc(k, &d.pts, 8 * B * MF)) || (rc = klt_alloc(k, &d.ids, 4 * B * MF)) || (rc = klt_alloc(k, &d.cnt, 4 * B)) ||
-      (rc = klt_alloc(k, &d.next_id, 4 * B)) || (rc = klt_alloc(k, &d.init, 4 * B)) || (rc = klt_alloc(k, &d.nxt, 8 * B * MF)) ||
-      (rc = klt_alloc(k, &d.status, B * MF)) || (rc = klt_alloc(k, &d.need, 4 * B)) || (rc = klt_alloc(k, &d.lmax, 8 * B)) ||
-      (rc = klt_alloc(k, &d.ckey, 8 * B * d.ccap)) || (rc = klt_alloc(k, &d.cidx, 4 * B * d.ccap)) ||
-      (rc = klt_alloc(k, &d.ccnt, 4 * B)) || (rc = klt_alloc(k, &d.feat, 16 * B * MF)) || (rc = klt_alloc(k, &d.oids, 4 * B * MF)) ||
-      (rc = klt_alloc(k, &d.ocnt, 4 * B)) || (rc = klt_alloc(k, &k->depth, 8 * B * MF)))
+  auto zeroed = [&](auto** p, long long count) { return k->own.alloc_zeroed(p, (size_t)count, k->stream); };
+  if ((rc = zeroed(&d.pyr, 2 * B * d.pyr_sz)) || (rc = zeroed(&d.par, B)) ||
+      (rc = zeroed(&d.mask, B * width * height)) || (rc = zeroed(&d.active, B)) ||
+      (rc = zeroed(&d.pts, 2 * B * MF)) || (rc = zeroed(&d.ids, B * MF)) || (rc = zeroed(&d.cnt, B)) ||
+      (rc = zeroed(&d.next_id, B)) || (rc = zeroed(&d.init, B)) || (rc = zeroed(&d.nxt, 2 * B * MF)) ||
+      (rc = zeroed(&d.status, B * MF)) || (rc = zeroed(&d.need, B)) || (rc = zeroed(&d.lmax, B)) ||
+      (rc = zeroed(&d.ckey, B * d.ccap)) || (rc = zeroed(&d.cidx, B * d.ccap)) ||
+      (rc = zeroed(&d.ccnt, B)) || (rc = zeroed(&d.feat, 2 * B * MF)) || (rc = zeroed(&d.oids, B * MF)) ||
+      (rc = zeroed(&d.ocnt, B)) || (rc = zeroed(&k->depth, B * MF)))
     return fin(rc);
   if (hipMemsetAsync(const_cast<uint8_t*>(d.mask), 255, (size_t)B * width * height, k->stream) != hipSuccess ||
       klt_clear_outputs(k) != VIEKF_OK)
@@ -725,8 +702,7 @@ int viekf_klt_destroy(viekf_klt* k) {
   if (!k) return fail(VIEKF_ERR_INVALID, "tracker is null");
   (void)hipSetDevice(k->device);
   if (k->stream) (void)hipStreamSynchronize(k->stream);
-  klt_free(k);
-  delete k;
+  klt_delete(k);
   return VIEKF_OK;
 }
 
@@ -773,12 +749,12 @@ int viekf_klt_sync(viekf_klt* k) {
 
 int viekf_klt_set_mask(viekf_klt* k, const uint8_t* mask, int32_t per_camera, viekf_mem where) {
   if (!k || !mask) return fail(VIEKF_ERR_INVALID, "null argument");
-  if (where != VIEKF_HOST && where != VIEKF_DEVICE) return fail(VIEKF_ERR_INVALID, "where must be VIEKF_HOST or VIEKF_DEVICE");
+  if (int rc = check_where(where)) return rc;
   if (int rc = set_dev(k)) return rc;
   KltDev& d = k->d;
   const long long n = (per_camera ? (long long)d.B : 1ll) * d.W * d.H;
   uint8_t* m = const_cast<uint8_t*>(d.mask);
-  HIP_TRY(hipMemcpyAsync(m, mask, n, where == VIEKF_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, k->stream));
+  if (int rc = copy_user(m, mask, n, where, Copy::FromUser, k->stream)) return rc;
   k_mask<<<(unsigned)((n + 255) / 256), 256, 0, k->stream>>>(m, n);
   HIP_TRY(hipGetLastError());
   d.mask_per_cam = per_camera != 0;
@@ -790,20 +766,21 @@ int viekf_klt_load_image(viekf_klt* k, const uint8_t* img, int32_t channels, con
                          int32_t* ids, int32_t* count, viekf_mem where) {
   if (!k || !img) return fail(VIEKF_ERR_INVALID, "null argument");
   if (channels != 1 && channels != 3) return fail(VIEKF_ERR_INVALID, "channels must be 1 (GRAY8) or 3 (BGR8)");
-  if (where != VIEKF_HOST && where != VIEKF_DEVICE) return fail(VIEKF_ERR_INVALID, "where must be VIEKF_HOST or VIEKF_DEVICE");
+  if (int rc = check_where(where)) return rc;
   if (int rc = set_dev(k)) return rc;
   KltDev& d = k->d;
   const long long B = d.B, MF = d.MF;
   const uint8_t* src = img;
   if (where == VIEKF_HOST) {
-    if (!k->img) HIP_TRY(hipMalloc(&k->img, (size_t)B * d.W * d.H * 3));
+    if (!k->img)
+      if (int rc = k->own.alloc(&k->img, (size_t)B * d.W * d.H * 3)) return rc;
     HIP_TRY(hipMemcpyAsync(k->img, img, (size_t)B * d.W * d.H * channels, hipMemcpyHostToDevice, k->stream));
     src = k->img;
   }
   uint8_t* act = const_cast<uint8_t*>(d.active);
-  if (active)
-    HIP_TRY(hipMemcpyAsync(act, active, B, where == VIEKF_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, k->stream));
-  else
+  if (active) {
+    if (int rc = copy_user(act, active, B, where, Copy::FromUser, k->stream)) return rc;
+  } else
     k_fill_active<<<(unsigned)((B + 255) / 256), 256, 0, k->stream>>>(act, (int)B);
   const unsigned qw = (d.W + 3) / 4;
   k_grey<<<dim3((qw * d.H + 255) / 256, B), 256, 0, k->stream>>>(d, src, channels);
@@ -848,12 +825,13 @@ int viekf_klt_drop_features(viekf_klt* k, const int32_t* ids, int32_t cnt, uint8
 
 int viekf_klt_sample_depth(viekf_klt* k, const float* depth_mm, double min_depth, double* depth, viekf_mem where) {
   if (!k || !depth_mm || !depth) return fail(VIEKF_ERR_INVALID, "null argument");
-  if (where != VIEKF_HOST && where != VIEKF_DEVICE) return fail(VIEKF_ERR_INVALID, "where must be VIEKF_HOST or VIEKF_DEVICE");
+  if (int rc = check_where(where)) return rc;
   if (int rc = set_dev(k)) return rc;
   const KltDev& d = k->d;
   const float* src = depth_mm;
   if (where == VIEKF_HOST) {
-    if (!k->dimg) HIP_TRY(hipMalloc(&k->dimg, sizeof(float) * d.B * d.W * d.H));
+    if (!k->dimg)
+      if (int rc = k->own.alloc(&k->dimg, (size_t)d.B * d.W * d.H)) return rc;
     HIP_TRY(hipMemcpyAsync(k->dimg, depth_mm, sizeof(float) * d.B * d.W * d.H, hipMemcpyHostToDevice, k->stream));
     src = k->dimg;
   }

@@ -15,10 +15,9 @@
 #include <cstdint>
 #include <cstring>
 #include <new>
-#include <string>
 
 #include "../../include/viekf_sim.h"
-#include "viekf_host.hpp"
+#include "viekf_hostkit.hpp"
 
 namespace {
 
@@ -524,15 +523,6 @@ __global__ void k_sim_init(SimDev d) {
   d.next_id[b] = 0;
 }
 
-int fail(int code, const std::string& msg) { return viekf::set_last_error(code, msg); }
-
-#define HIP_TRY(expr)                                                                                  \
-  do {                                                                                                 \
-    hipError_t e_ = (expr);                                                                            \
-    if (e_ != hipSuccess)                                                                              \
-      return fail(VIEKF_ERR_HIP, std::string(#expr) + " failed: " + hipGetErrorString(e_));            \
-  } while (0)
-
 }  // namespace
 
 struct viekf_sim {
@@ -540,71 +530,46 @@ struct viekf_sim {
   int device = 0;
   hipStream_t stream = nullptr;
   bool own_stream = false;
+  DevOwner own;                                   // every device buffer below
   long long tick = 0;
   // per-vehicle values and the landmark field (owned; SimDev holds const views of them)
   unsigned long long* seed = nullptr;
   double *radius = nullptr, *period = nullptr, *ab = nullptr, *gb = nullptr, *lm = nullptr, *amp = nullptr;
-  size_t lm_bytes = 0;                            // capacity of lm: one field until a per-vehicle one is set
-  // growable device staging for callers with host pointers
-  void* stage[2] = {nullptr, nullptr};
+  size_t lm_count = 0;                            // capacity of lm in doubles: one field until a per-vehicle one is set
+  // growable device staging for callers with host pointers (bytes)
+  char* stage[2] = {nullptr, nullptr};
   size_t stage_sz[2] = {0, 0};
-  void* bufs[24] = {};
-  int nbufs = 0;
 };
 
 namespace {
 
-template <class T>
-int sim_alloc(viekf_sim* s, T** p, size_t bytes) {
-  void* q = nullptr;
-  HIP_TRY(hipMalloc(&q, bytes ? bytes : 1));
-  HIP_TRY(hipMemsetAsync(q, 0, bytes ? bytes : 1, s->stream));
-  s->bufs[s->nbufs++] = q;
-  *p = static_cast<T*>(q);
-  return VIEKF_OK;
-}
-
-void sim_free(viekf_sim* s) {
-  for (int i = 0; i < s->nbufs; i++) (void)hipFree(s->bufs[i]);
-  s->nbufs = 0;
-  for (int i = 0; i < 2; i++)
-    if (s->stage[i]) (void)hipFree(s->stage[i]);
-  if (s->lm) (void)hipFree(s->lm);
+// the end of a simulator (the caller has set the device and waited for its stream)
+void sim_delete(viekf_sim* s) {
+  s->own.release_all();
   if (s->own_stream && s->stream) (void)hipStreamDestroy(s->stream);
+  delete s;
 }
 
 // device staging buffer `i` of at least `bytes` (for callers with host pointers)
-int sim_stage(viekf_sim* s, int i, size_t bytes, void** out) {
-  if (s->stage_sz[i] < bytes) {
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    if (s->stage[i]) HIP_TRY(hipFree(s->stage[i]));
-    s->stage[i] = nullptr;
-    s->stage_sz[i] = 0;
-    HIP_TRY(hipMalloc(&s->stage[i], bytes));
-    s->stage_sz[i] = bytes;
-  }
-  *out = s->stage[i];
+template <class T>
+int sim_stage(viekf_sim* s, int i, size_t bytes, T** out) {
+  if (int rc = s->own.reserve(&s->stage[i], &s->stage_sz[i], bytes, s->stream)) return rc;
+  *out = reinterpret_cast<T*>(s->stage[i]);
   return VIEKF_OK;
 }
 
 int copy_out(viekf_sim* s, void* dst, const void* src, size_t bytes, viekf_mem where) {
-  if (!dst) return VIEKF_OK;
-  HIP_TRY(hipMemcpyAsync(dst, src, bytes, where == VIEKF_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, s->stream));
-  return VIEKF_OK;
+  return copy_user(dst, src, bytes, where, Copy::ToUser, s->stream);
 }
 
 int copy_in(viekf_sim* s, void* dst, const void* src, size_t bytes, viekf_mem where) {
-  if (!src) return VIEKF_OK;
-  HIP_TRY(hipMemcpyAsync(dst, src, bytes, where == VIEKF_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s->stream));
-  return VIEKF_OK;
+  return copy_user(dst, src, bytes, where, Copy::FromUser, s->stream);
 }
 
 int set_dev(const viekf_sim* s) {
   HIP_TRY(hipSetDevice(s->device));
   return VIEKF_OK;
 }
-
-int bad_where(viekf_mem where) { return where != VIEKF_HOST && where != VIEKF_DEVICE; }
 
 // x0, tick 0, nothing tracked, then the constructor's _control()
 int sim_restart(viekf_sim* s) {
@@ -663,17 +628,18 @@ int viekf_sim_create(int32_t batch, const viekf_params* p, const viekf_sim_confi
   for (int i = 0; i < 4; i++) { d.qbc[i] = p->q_b_c[i]; d.qbu[i] = p->q_b_u[i]; }
   for (int i = 0; i < 3; i++) d.pbc[i] = p->p_b_c[i];
   int rc = VIEKF_OK;
-  auto fin = [&](int code) { sim_free(s); delete s; return code; };
+  auto fin = [&](int code) { sim_delete(s); return code; };
   if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) return fin(fail(VIEKF_ERR_HIP, "hipStreamCreate failed"));
   s->own_stream = true;
   const size_t B = batch, MF = d.MF, L = d.L;
-  if ((rc = sim_alloc(s, &d.st, 8 * kStateFields * B)) || (rc = sim_alloc(s, &s->seed, 8 * B)) || (rc = sim_alloc(s, &s->radius, 8 * B)) ||
-      (rc = sim_alloc(s, &s->period, 8 * B)) || (rc = sim_alloc(s, &s->ab, 24 * B)) || (rc = sim_alloc(s, &s->gb, 24 * B)) ||
-      (rc = sim_alloc(s, &s->amp, 8 * L)) || (rc = sim_alloc(s, &d.trk, 4 * B * MF)) ||
-      (rc = sim_alloc(s, &d.tid, 4 * B * MF)) || (rc = sim_alloc(s, &d.tcnt, 4 * B)) || (rc = sim_alloc(s, &d.next_id, 4 * B)))
+  auto zeroed = [&](auto** p, size_t count) { return s->own.alloc_zeroed(p, count, s->stream); };
+  if ((rc = zeroed(&d.st, kStateFields * B)) || (rc = zeroed(&s->seed, B)) || (rc = zeroed(&s->radius, B)) ||
+      (rc = zeroed(&s->period, B)) || (rc = zeroed(&s->ab, 3 * B)) || (rc = zeroed(&s->gb, 3 * B)) ||
+      (rc = zeroed(&s->amp, L)) || (rc = zeroed(&d.trk, B * MF)) ||
+      (rc = zeroed(&d.tid, B * MF)) || (rc = zeroed(&d.tcnt, B)) || (rc = zeroed(&d.next_id, B)))
     return fin(rc);
-  if (hipMalloc(reinterpret_cast<void**>(&s->lm), 24 * L) != hipSuccess) return fin(fail(VIEKF_ERR_HIP, "hipMalloc of the landmark field failed"));
-  s->lm_bytes = 24 * L;
+  if (s->own.alloc(&s->lm, 3 * L)) return fin(fail(VIEKF_ERR_HIP, "hipMalloc of the landmark field failed"));
+  s->lm_count = 3 * L;
   d.seed = s->seed; d.radius = s->radius; d.period = s->period; d.ab = s->ab; d.gb = s->gb; d.lm = s->lm; d.amp = s->amp;
   // defaults: sim.py's per-vehicle values, the regular grid (after the allocations' clears, which run on the stream)
   if (hipStreamSynchronize(s->stream) != hipSuccess) return fin(fail(VIEKF_ERR_HIP, "clearing the simulator's buffers failed"));
@@ -716,8 +682,7 @@ int viekf_sim_destroy(viekf_sim* s) {
   if (!s) return fail(VIEKF_ERR_INVALID, "simulator is null");
   (void)hipSetDevice(s->device);
   if (s->stream) (void)hipStreamSynchronize(s->stream);
-  sim_free(s);
-  delete s;
+  sim_delete(s);
   return VIEKF_OK;
 }
 
@@ -758,7 +723,7 @@ int viekf_sim_sync(viekf_sim* s) {
 int viekf_sim_set_vehicles(viekf_sim* s, const uint64_t* seed, const double* radius, const double* period, const double* accel_bias,
                            const double* gyro_bias, viekf_mem where) {
   if (!s) return fail(VIEKF_ERR_INVALID, "simulator is null");
-  if (bad_where(where)) return fail(VIEKF_ERR_INVALID, "where must be VIEKF_HOST or VIEKF_DEVICE");
+  if (int rc = check_where(where)) return rc;
   if (int rc = set_dev(s)) return rc;
   const size_t B = s->d.B;
   if (period && where == VIEKF_HOST)
@@ -775,17 +740,17 @@ int viekf_sim_set_vehicles(viekf_sim* s, const uint64_t* seed, const double* rad
 
 int viekf_sim_set_landmarks(viekf_sim* s, const double* lm, int32_t per_vehicle, viekf_mem where) {
   if (!s || !lm) return fail(VIEKF_ERR_INVALID, "null argument");
-  if (bad_where(where)) return fail(VIEKF_ERR_INVALID, "where must be VIEKF_HOST or VIEKF_DEVICE");
+  if (int rc = check_where(where)) return rc;
   if (int rc = set_dev(s)) return rc;
   SimDev& d = s->d;
   const size_t n = (per_vehicle ? (size_t)d.B : 1) * d.L * 3;
-  if (s->lm_bytes < 8 * n) {                      // the first per-vehicle field: room for one field per vehicle
+  if (s->lm_count < n) {                          // the first per-vehicle field: room for one field per vehicle
     HIP_TRY(hipStreamSynchronize(s->stream));
-    double* q = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&q), 8 * n));
-    (void)hipFree(s->lm);
+    double* q = nullptr;                          // (the old field stays if this fails: alloc, then free)
+    if (int rc = s->own.alloc(&q, n)) return rc;
+    (void)s->own.free(&s->lm);
     s->lm = q;
-    s->lm_bytes = 8 * n;
+    s->lm_count = n;
     d.lm = q;
   }
   if (int rc = copy_in(s, s->lm, lm, 8 * n, where)) return rc;
@@ -798,13 +763,13 @@ int viekf_sim_set_landmarks(viekf_sim* s, const double* lm, int32_t per_vehicle,
 
 int viekf_sim_imu(viekf_sim* s, double* u, viekf_mem where) {
   if (!s || !u) return fail(VIEKF_ERR_INVALID, "null argument");
-  if (bad_where(where)) return fail(VIEKF_ERR_INVALID, "where must be VIEKF_HOST or VIEKF_DEVICE");
+  if (int rc = check_where(where)) return rc;
   if (where == VIEKF_DEVICE && (reinterpret_cast<uintptr_t>(u) & 15)) return fail(VIEKF_ERR_INVALID, "u must be 16-byte aligned");
   if (int rc = set_dev(s)) return rc;
   const size_t bytes = 48 * (size_t)s->d.B;
   double* du = u;
   if (where == VIEKF_HOST)
-    if (int rc = sim_stage(s, 0, bytes, reinterpret_cast<void**>(&du))) return rc;
+    if (int rc = sim_stage(s, 0, bytes, &du)) return rc;
   k_sim_step<<<(unsigned)((s->d.B + 63) / 64), 64, 0, s->stream>>>(s->d, s->tick, 0, 2, du);
   HIP_TRY(hipGetLastError());
   if (where == VIEKF_HOST) {
@@ -817,13 +782,13 @@ int viekf_sim_imu(viekf_sim* s, double* u, viekf_mem where) {
 int viekf_sim_step(viekf_sim* s, int32_t K, double* u, viekf_mem where) {
   if (!s || !u) return fail(VIEKF_ERR_INVALID, "null argument");
   if (K < 1 || K > (1 << 20)) return fail(VIEKF_ERR_INVALID, "K must be in [1, 2^20]");
-  if (bad_where(where)) return fail(VIEKF_ERR_INVALID, "where must be VIEKF_HOST or VIEKF_DEVICE");
+  if (int rc = check_where(where)) return rc;
   if (where == VIEKF_DEVICE && (reinterpret_cast<uintptr_t>(u) & 15)) return fail(VIEKF_ERR_INVALID, "u must be 16-byte aligned");
   if (int rc = set_dev(s)) return rc;
   const size_t bytes = 48 * (size_t)s->d.B * K;
   double* du = u;
   if (where == VIEKF_HOST)
-    if (int rc = sim_stage(s, 0, bytes, reinterpret_cast<void**>(&du))) return rc;
+    if (int rc = sim_stage(s, 0, bytes, &du)) return rc;
   k_sim_step<<<(unsigned)((s->d.B + 63) / 64), 64, 0, s->stream>>>(s->d, s->tick, K, 0, du);
   HIP_TRY(hipGetLastError());
   s->tick += K;
@@ -838,7 +803,7 @@ int viekf_sim_camera(viekf_sim* s, int32_t num_features, double* z, int32_t* ids
                      viekf_mem where) {
   if (!s || !z || !ids || !count) return fail(VIEKF_ERR_INVALID, "null argument (z, ids and count are required)");
   if (num_features < 1 || num_features > s->d.MF) return fail(VIEKF_ERR_INVALID, "num_features must be in [1, max_features of viekf_sim_create]");
-  if (bad_where(where)) return fail(VIEKF_ERR_INVALID, "where must be VIEKF_HOST or VIEKF_DEVICE");
+  if (int rc = check_where(where)) return rc;
   if (int rc = set_dev(s)) return rc;
   const size_t B = s->d.B, N = num_features;
   if (where == VIEKF_DEVICE) {                    // the kernel writes the caller's arrays
@@ -848,7 +813,7 @@ int viekf_sim_camera(viekf_sim* s, int32_t num_features, double* z, int32_t* ids
   }
   // host pointers: one staging block  z | depth | ids | landmark | count
   char* st = nullptr;
-  if (int rc = sim_stage(s, 0, 32 * B * N + 4 * B, reinterpret_cast<void**>(&st))) return rc;
+  if (int rc = sim_stage(s, 0, 32 * B * N + 4 * B, &st)) return rc;
   double *dz = reinterpret_cast<double*>(st), *dd = reinterpret_cast<double*>(st + 16 * B * N);
   int *di = reinterpret_cast<int*>(st + 24 * B * N), *dl = reinterpret_cast<int*>(st + 28 * B * N), *dc = reinterpret_cast<int*>(st + 32 * B * N);
   k_sim_camera<<<(unsigned)B, kCamThreads, 0, s->stream>>>(s->d, s->tick, num_features, dz, di, dc, depth ? dd : nullptr, landmark ? dl : nullptr);
@@ -866,7 +831,7 @@ int viekf_sim_render(viekf_sim* s, int32_t width, int32_t height, uint8_t* img, 
   if (!s || !img) return fail(VIEKF_ERR_INVALID, "null argument");
   if (width < 4 || height < 4 || width > 16384 || height > 16384) return fail(VIEKF_ERR_INVALID, "width and height must be in [4, 16384]");
   if (width & 1) return fail(VIEKF_ERR_INVALID, "width must be even: pixels are stored in pairs (in groups of four when width % 4 == 0)");
-  if (bad_where(where)) return fail(VIEKF_ERR_INVALID, "where must be VIEKF_HOST or VIEKF_DEVICE");
+  if (int rc = check_where(where)) return rc;
   if (where == VIEKF_DEVICE && ((reinterpret_cast<uintptr_t>(img) & 3) || (reinterpret_cast<uintptr_t>(depth_mm) & 15)))
     return fail(VIEKF_ERR_INVALID, "img must be 4-byte and depth_mm 16-byte aligned");
   if (int rc = set_dev(s)) return rc;
@@ -874,9 +839,9 @@ int viekf_sim_render(viekf_sim* s, int32_t width, int32_t height, uint8_t* img, 
   uint8_t* di = img;
   float* dd = depth_mm;
   if (where == VIEKF_HOST) {
-    if (int rc = sim_stage(s, 0, npx, reinterpret_cast<void**>(&di))) return rc;
+    if (int rc = sim_stage(s, 0, npx, &di)) return rc;
     if (depth_mm)
-      if (int rc = sim_stage(s, 1, 4 * npx, reinterpret_cast<void**>(&dd))) return rc;
+      if (int rc = sim_stage(s, 1, 4 * npx, &dd)) return rc;
   }
   const int tx = (width + kTileW - 1) / kTileW, ty = (height + kTileH - 1) / kTileH;
   k_sim_render<<<dim3((unsigned)(tx * ty), (unsigned)s->d.B), 256, 0, s->stream>>>(s->d, width, height, tx, di, dd);
@@ -891,7 +856,7 @@ int viekf_sim_render(viekf_sim* s, int32_t width, int32_t height, uint8_t* img, 
 
 int viekf_sim_get_truth(viekf_sim* s, double* state, double* t, viekf_mem where) {
   if (!s || (!state && !t)) return fail(VIEKF_ERR_INVALID, "null argument");
-  if (bad_where(where)) return fail(VIEKF_ERR_INVALID, "where must be VIEKF_HOST or VIEKF_DEVICE");
+  if (int rc = check_where(where)) return rc;
   if (int rc = set_dev(s)) return rc;
   const size_t B = s->d.B;
   double *ds = state, *dt = t;
@@ -914,7 +879,7 @@ int viekf_sim_get_truth(viekf_sim* s, double* state, double* t, viekf_mem where)
 int viekf_sim_truth_state(viekf_sim* s, const int32_t* ids, int32_t N, double* x_true, viekf_mem where) {
   if (!s || !x_true || (!ids && N > 0)) return fail(VIEKF_ERR_INVALID, "null argument");
   if (N < 0 || N > s->d.MF) return fail(VIEKF_ERR_INVALID, "N must be in [0, max_features of viekf_sim_create]");
-  if (bad_where(where)) return fail(VIEKF_ERR_INVALID, "where must be VIEKF_HOST or VIEKF_DEVICE");
+  if (int rc = check_where(where)) return rc;
   if (int rc = set_dev(s)) return rc;
   const size_t B = s->d.B, nx = 17 + 5 * (size_t)N;
   const int* dids = ids;

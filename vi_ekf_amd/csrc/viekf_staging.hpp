@@ -15,16 +15,7 @@ size_t stage_size(size_t bytes) { return bytes + 256; }
 // bump allocator over one device staging region (host-pointer calls only)
 int stage_begin(viekf_batch* b, size_t need) {
   need += 4096;
-  if (need > b->stage_bytes) {
-    if (b->d_stage) {
-      HIP_TRY(hipStreamSynchronize(b->stream));
-      HIP_TRY(hipFree(b->d_stage));
-      b->d_stage = nullptr;
-      b->stage_bytes = 0;
-    }
-    HIP_TRY(hipMalloc(&b->d_stage, need));
-    b->stage_bytes = need;
-  }
+  if (int rc = b->own.reserve(&b->d_stage, &b->stage_bytes, need, b->stream)) return rc;
   b->stage_used = 0;
   if (b->async_host) {
     // A pinned RING on the host side (the copies out of it run later, in stream order) and a ring on the device side too: the

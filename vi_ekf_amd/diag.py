@@ -5,12 +5,14 @@ would see.  Plumbing only -- the numbers come from libviekf_hip.so (csrc/viekf_k
 Arguments may be numpy arrays (host pointers, numpy results) or torch tensors on the batch's device (device pointers,
 torch results).  With device tensors `consistency` returns once its work is queued on the batch's stream -- `batch.sync()` or
 a stream shared with torch orders it -- while `innovation` waits for it: it hands the library re-laid-out copies of z and R
-that must outlive the kernel."""
+that must outlive the kernel.  (`innovation` re-lays R out itself, not with _dev.r_colmajor: rdim is general here and r_mode
+may be given.)"""
 import ctypes as C
 
 import numpy as np
 
 from . import capi
+from ._dev import empty, is_torch
 
 # every symbol include/viekf_diag.h declares (tests check the library exports exactly these)
 DIAG_SYMBOLS = ["viekf_diag_consistency", "viekf_diag_innovation"]
@@ -29,18 +31,9 @@ def _bind():
     return L
 
 
-def _is_torch(a):
-    return hasattr(a, "data_ptr") and hasattr(a, "is_cuda")
-
-
 def _empty(batch, shape, dtype, like):
-    """an output array on the side of `like` (a torch device tensor or anything else) -> (array, pointer)"""
-    if like is not None and _is_torch(like):
-        import torch
-        t = torch.empty(shape, dtype={np.float64: torch.float64, np.int32: torch.int32}[dtype], device=like.device)
-        return t, C.c_void_p(t.data_ptr())
-    arr = np.empty(shape, dtype=dtype)
-    return arr, C.c_void_p(arr.ctypes.data)
+    """an output array on the side of `like` (a torch tensor on the batch's device, or anything else) -> (array, pointer)"""
+    return empty(shape, dtype, batch.device if like is not None and is_torch(like) else None)
 
 
 def consistency(batch, x_true=None):
@@ -77,19 +70,19 @@ def innovation(batch, mtype, z, R, slot=None, r_mode=None):
     M = 1 if squeeze else int(z.shape[1])
     zdim = int(z.shape[-1])
     rdim = int(R.shape[-1])
-    tr = (lambda t: t.transpose(-1, -2).contiguous()) if _is_torch(R) else (lambda t: np.ascontiguousarray(np.swapaxes(np.asarray(t, dtype=np.float64), -1, -2)))
+    tr = (lambda t: t.transpose(-1, -2).contiguous()) if is_torch(R) else (lambda t: np.ascontiguousarray(np.swapaxes(np.asarray(t, dtype=np.float64), -1, -2)))
     if r_mode is None:
         r_mode = len(R.shape) - 2
     want = {0: (rdim, rdim), 1: (B, rdim, rdim), 2: (B, M, rdim, rdim)}.get(r_mode)
     if want is None or tuple(R.shape) != want:
         raise ValueError("R must be (rdim,rdim), (B,rdim,rdim) or (B,M,rdim,rdim), matching r_mode")
     Rc = tr(R)   # the ABI takes column-major
-    zc = z.reshape(B, M, zdim) if _is_torch(z) else np.asarray(z, dtype=np.float64).reshape(B, M, zdim)
+    zc = z.reshape(B, M, zdim) if is_torch(z) else np.asarray(z, dtype=np.float64).reshape(B, M, zdim)
     pz, where = batch._arg(zc, np.float64, (B, M, zdim), None)
     pR, where = batch._arg(Rc, np.float64, tuple(Rc.shape), where)
     ps = None
     if slot is not None:
-        sc = slot.reshape(B, M) if _is_torch(slot) else np.asarray(slot, dtype=np.int32).reshape(B, M)
+        sc = slot.reshape(B, M) if is_torch(slot) else np.asarray(slot, dtype=np.int32).reshape(B, M)
         ps, where = batch._arg(sc, np.int32, (B, M), where)
     nis, pn = _empty(batch, (B, M), np.float64, z)
     res, pr = _empty(batch, (B, M, 3), np.float64, z)
@@ -101,7 +94,7 @@ def innovation(batch, mtype, z, R, slot=None, r_mode=None):
     del keep
     batch._keep = []
     Sm = S[:, :, :rdim * rdim].reshape(B, M, rdim, rdim)
-    Sm = Sm.transpose(-1, -2) if _is_torch(Sm) else np.swapaxes(Sm, -1, -2)
+    Sm = Sm.transpose(-1, -2) if is_torch(Sm) else np.swapaxes(Sm, -1, -2)
     out = dict(nis=nis, residual=res[:, :, :rdim], S=Sm)
     if squeeze:
         out = {k: v[:, 0] for k, v in out.items()}

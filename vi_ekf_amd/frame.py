@@ -12,6 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
+from ._dev import Companion, r_colmajor
 
 # every symbol include/viekf_frame.h declares (tests check the library exports exactly these)
 FRAME_SYMBOLS = ["viekf_frame_create", "viekf_frame_destroy", "viekf_frame_reset", "viekf_frame_set_tracked",
@@ -19,61 +20,20 @@ FRAME_SYMBOLS = ["viekf_frame_create", "viekf_frame_destroy", "viekf_frame_reset
 MAX_M = 4096     # VIEKF_FRAME_MAX_M
 
 
-def _is_torch(a):
-    return hasattr(a, "data_ptr") and hasattr(a, "is_cuda")
-
-
-class FrameIntake:
+class FrameIntake(Companion):
     """
         fi = FrameIntake(batch)
         out = fi.intake(z, ids, R_pix)         # dict(result [B][M], gated [B][M], gated_count [B], did_reset [B], edges [B][17])
         ids, ln = fi.tracked()                  # [B][N] -1 padded in slot order (BatchSimulator.truth_state takes it), [B]
     """
 
+    _destroy = "viekf_frame_destroy"
+
     def __init__(self, batch):
-        self._L = capi.lib()
-        self._h = None
-        self.batch = batch      # (the batch must outlive the intake: it stays referenced from here)
-        self._alive()
+        super().__init__(capi.lib(), batch)
         h = C.c_void_p()
         capi.check(self._L.viekf_frame_create(batch._h, C.byref(h)))
         self._h = h
-
-    def _alive(self):
-        if getattr(self.batch, "_h", None) is None or not self.batch._h.value:
-            raise ValueError("the batch of this FrameIntake has been closed")
-
-    def close(self):
-        if self._h:
-            self._L.viekf_frame_destroy(self._h)   # (the tables can go after their batch has)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _handle(self):
-        if not self._h:
-            raise ValueError("this FrameIntake has been closed")
-        self._alive()
-        return self._h
-
-    def _empty(self, shape, dtype, device):
-        if device:
-            import torch
-            t = torch.empty(shape, dtype=getattr(torch, np.dtype(dtype).name), device="cuda:%d" % self.batch.device)
-            return t, C.c_void_p(t.data_ptr())
-        a = np.empty(shape, dtype=dtype)
-        return a, C.c_void_p(a.ctypes.data)
-
-    def _ready(self, device, sync):
-        """device outputs come from torch's caching allocator and the inputs may still be in torch's queue, while the
-        work runs on the batch's stream (as BatchSimulator does)"""
-        if device and sync:
-            import torch
-            torch.cuda.synchronize(self.batch.device)
 
     def reset(self):
         """no ids tracked, no keyframe list (pairs with BatchVIEKF.reset)"""
@@ -88,9 +48,7 @@ class FrameIntake:
         p, w = g._arg(ids, np.int32, (g.B, g.N), None)
         self._ready(w == capi.DEVICE, True)
         capi.check(self._L.viekf_frame_set_tracked(h, p, w))
-        if w == capi.DEVICE:
-            g.sync()
-        g._keep = []
+        self._done(w == capi.DEVICE, True)
 
     def tracked(self, device=False):
         """-> (ids [B][N] -1 padded in slot order, len [B])"""
@@ -100,8 +58,7 @@ class FrameIntake:
         ln, pl = self._empty((g.B,), np.int32, device)
         self._ready(device, True)
         capi.check(self._L.viekf_frame_tracked(h, pi, pl, capi.DEVICE if device else capi.HOST))
-        if device:
-            g.sync()
+        self._done(device, True)
         return ids, ln
 
     def intake(self, z, ids, R, depth=None, active=None, sync=True):
@@ -119,18 +76,7 @@ class FrameIntake:
         M = int(ids.shape[1])
         pz, w = g._arg(z, np.float64, (B, M, 2), None)
         pi, w = g._arg(ids, np.int32, (B, M), w)
-        Rshape = tuple(R.shape)
-        if Rshape == (2, 2):       # the ABI takes column-major 2x2
-            r_mode = 0
-            Rc = R.t().contiguous() if _is_torch(R) else np.ascontiguousarray(np.asarray(R, dtype=np.float64).T)
-        elif Rshape == (B, 2, 2):
-            r_mode = 1
-            Rc = R.transpose(1, 2).contiguous() if _is_torch(R) else np.ascontiguousarray(np.asarray(R, dtype=np.float64).transpose(0, 2, 1))
-        elif Rshape == (B, M, 2, 2):
-            r_mode = 2
-            Rc = R.transpose(2, 3).contiguous() if _is_torch(R) else np.ascontiguousarray(np.asarray(R, dtype=np.float64).transpose(0, 1, 3, 2))
-        else:
-            raise ValueError("R must be (2,2), (B,2,2) or (B,M,2,2)")
+        Rc, r_mode = r_colmajor(R, B, M)
         pR, w = g._arg(Rc, np.float64, tuple(Rc.shape), w)
         pd, w = g._arg(depth, np.float64, (B, M), w)
         pa, w = g._arg(active, np.uint8, (B,), w)
@@ -143,9 +89,7 @@ class FrameIntake:
         out["edges"], pe = self._empty((B, 17), np.float64, dev)
         self._ready(dev, sync)
         capi.check(self._L.viekf_frame_intake(h, M, pz, pi, pd, pR, r_mode, pa, pres, pg, pgc, pdr, pe, w))
-        if dev and sync:
-            g.sync()
-        elif dev:
+        if dev and not sync:
             self._pending = (z, ids, Rc, depth, active)   # (re-laid-out R must outlive the queued work)
-        g._keep = []
+        self._done(dev, sync)
         return out

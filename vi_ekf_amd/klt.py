@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
+from ._dev import Handle, is_torch
 
 # every symbol include/viekf_klt.h declares (tests check the library exports exactly these)
 KLT_SYMBOLS = [
@@ -45,19 +46,17 @@ def _p(a):
     return C.c_void_p(a.ctypes.data)
 
 
-def _is_torch(a):
-    return type(a).__module__.startswith("torch")
-
-
-class KLTTracker:
+class KLTTracker(Handle):
     """`batch` KLT_Tracker instances (reference include/klt_tracker.h) of one image size, on one device.
 
         trk = KLTTracker(B, 640, 480, max_features=50, radius=30)
         feats, ids, count = trk.load_image(frames)      # frames [B][H][W] (GRAY8) or [B][H][W][3] (BGR8)
     """
 
+    _destroy = "viekf_klt_destroy"
+
     def __init__(self, batch, width, height, max_features=12, radius=30, invert_image=False, device=0):
-        self._L = _bind()
+        super().__init__(_bind())
         self.B, self.W, self.H = int(batch), int(width), int(height)
         self.MF, self.radius, self.invert = int(max_features), int(radius), bool(invert_image)
         self.device = int(device)
@@ -66,30 +65,22 @@ class KLTTracker:
                                             C.byref(h)))
         self._h = h
         lv = C.c_int32()
-        capi.check(self._L.viekf_klt_dims(self._h, None, None, None, None, None, C.byref(lv)))
+        capi.check(self._L.viekf_klt_dims(self._handle(), None, None, None, None, None, C.byref(lv)))
         self.levels = lv.value
 
-    def __del__(self):
-        try:
-            if self._h:
-                self._L.viekf_klt_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
     def reset(self):
-        capi.check(self._L.viekf_klt_reset(self._h))
+        capi.check(self._L.viekf_klt_reset(self._handle()))
 
     def set_stream(self, stream):
         """a hipStream_t handle (int, e.g. torch.cuda.current_stream().cuda_stream) or None for the null stream"""
-        capi.check(self._L.viekf_klt_set_stream(self._h, None if stream is None else C.c_void_p(int(stream))))
+        capi.check(self._L.viekf_klt_set_stream(self._handle(), None if stream is None else C.c_void_p(int(stream))))
 
     def sync(self):
-        capi.check(self._L.viekf_klt_sync(self._h))
+        capi.check(self._L.viekf_klt_sync(self._handle()))
 
     def _frame_arg(self, a, dtype):
         """-> (pointer, keep-alive, where) of a host array or a device tensor"""
-        if _is_torch(a):
+        if is_torch(a):
             import torch
             if a.is_cuda:
                 t = a.contiguous()
@@ -105,7 +96,7 @@ class KLTTracker:
         per = len(mask.shape) == 3
         assert tuple(mask.shape[-2:]) == (self.H, self.W) and (not per or mask.shape[0] == self.B)
         p, keep, where = self._frame_arg(mask, np.uint8)
-        capi.check(self._L.viekf_klt_set_mask(self._h, p, int(per), where))
+        capi.check(self._L.viekf_klt_set_mask(self._handle(), p, int(per), where))
         del keep
 
     def load_image(self, frames, active=None):
@@ -124,8 +115,8 @@ class KLTTracker:
             cnt = torch.empty(self.B, dtype=torch.int32, device=dev)
             act = None
             if active is not None:
-                act = torch.as_tensor(np.asarray(active, np.uint8) if not _is_torch(active) else active).to(dev, torch.uint8).contiguous()
-            capi.check(self._L.viekf_klt_load_image(self._h, p, ch, None if act is None else C.c_void_p(act.data_ptr()),
+                act = torch.as_tensor(np.asarray(active, np.uint8) if not is_torch(active) else active).to(dev, torch.uint8).contiguous()
+            capi.check(self._L.viekf_klt_load_image(self._handle(), p, ch, None if act is None else C.c_void_p(act.data_ptr()),
                                                     C.c_void_p(feats.data_ptr()), C.c_void_p(ids.data_ptr()),
                                                     C.c_void_p(cnt.data_ptr()), capi.DEVICE))
             self.sync()
@@ -134,7 +125,7 @@ class KLTTracker:
         ids = np.empty((self.B, self.MF), np.int32)
         cnt = np.empty(self.B, np.int32)
         act = None if active is None else np.ascontiguousarray(active, dtype=np.uint8).reshape(self.B)
-        capi.check(self._L.viekf_klt_load_image(self._h, p, ch, None if act is None else _p(act), _p(feats), _p(ids), _p(cnt),
+        capi.check(self._L.viekf_klt_load_image(self._handle(), p, ch, None if act is None else _p(act), _p(feats), _p(ids), _p(cnt),
                                                 capi.HOST))
         return feats, ids, cnt
 
@@ -142,7 +133,7 @@ class KLTTracker:
         """KLT_Tracker::drop_feature for ids [B][k] (-1 = none) -> found [B][k] bool"""
         ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(self.B, -1)
         found = np.zeros(ids.shape, np.uint8)
-        capi.check(self._L.viekf_klt_drop_features(self._h, _p(ids), ids.shape[1], _p(found)))
+        capi.check(self._L.viekf_klt_drop_features(self._handle(), _p(ids), ids.shape[1], _p(found)))
         return found.astype(bool)
 
     def sample_depth(self, depth_mm, min_depth):
@@ -153,11 +144,11 @@ class KLTTracker:
         if where == capi.DEVICE:
             import torch
             out = torch.empty((self.B, self.MF), dtype=torch.float64, device=keep.device)
-            capi.check(self._L.viekf_klt_sample_depth(self._h, p, float(min_depth), C.c_void_p(out.data_ptr()), capi.DEVICE))
+            capi.check(self._L.viekf_klt_sample_depth(self._handle(), p, float(min_depth), C.c_void_p(out.data_ptr()), capi.DEVICE))
             self.sync()
             return out
         out = np.empty((self.B, self.MF))
-        capi.check(self._L.viekf_klt_sample_depth(self._h, p, float(min_depth), _p(out), capi.HOST))
+        capi.check(self._L.viekf_klt_sample_depth(self._handle(), p, float(min_depth), _p(out), capi.HOST))
         return out
 
     def get_points(self):
@@ -166,7 +157,7 @@ class KLTTracker:
         ids = np.zeros((self.B, self.MF), np.int32)
         cnt = np.zeros(self.B, np.int32)
         nid = np.zeros(self.B, np.int32)
-        capi.check(self._L.viekf_klt_get_points(self._h, _p(pts), _p(ids), _p(cnt), _p(nid)))
+        capi.check(self._L.viekf_klt_get_points(self._handle(), _p(pts), _p(ids), _p(cnt), _p(nid)))
         return [pts[b, :cnt[b]].copy() for b in range(self.B)], [ids[b, :cnt[b]].copy() for b in range(self.B)], nid
 
     def level_shape(self, level):
@@ -178,7 +169,7 @@ class KLTTracker:
     def get_level(self, level):
         """pyramid level `level` of the last frame -> [B][h_l][w_l] u8"""
         out = np.zeros((self.B,) + self.level_shape(level), np.uint8)
-        capi.check(self._L.viekf_klt_get_level(self._h, int(level), _p(out)))
+        capi.check(self._L.viekf_klt_get_level(self._handle(), int(level), _p(out)))
         return out
 
 
@@ -196,12 +187,12 @@ def track_frame(seq, tracker, t, frames, feat_R, depth_mm=None, depth_R=None, mi
     B, MF = tracker.B, tracker.MF
     assert seq.B == B, "one filter per camera"
     feats, ids, cnt = tracker.load_image(frames, active=active)
-    if _is_torch(feats):
+    if is_torch(feats):
         feats, ids, cnt = feats.cpu().numpy(), ids.cpu().numpy(), cnt.cpu().numpy()
     depth = None
     if depth_mm is not None:
         depth = tracker.sample_depth(depth_mm, seq.core.params.min_depth if min_depth is None else min_depth)
-        if _is_torch(depth):
+        if is_torch(depth):
             depth = depth.cpu().numpy()
     seq.keep_only_features(ids)
     zdepth = depth if (depth is not None and use_depth) else np.full((B, MF), np.nan)

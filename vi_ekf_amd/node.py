@@ -12,6 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
+from ._dev import Companion
 
 # every symbol include/viekf_node.h declares (tests check the library exports exactly these)
 NODE_SYMBOLS = ["viekf_node_create", "viekf_node_destroy", "viekf_node_reset", "viekf_node_update", "viekf_node_global",
@@ -38,11 +39,7 @@ def _bind():
     return L
 
 
-def _is_torch(a):
-    return hasattr(a, "data_ptr") and hasattr(a, "is_cuda")
-
-
-class NodeGraph:
+class NodeGraph(Companion):
     """
         ng = NodeGraph(batch, trail_capacity=0)
         out = fi.intake(z, ids, R_pix)
@@ -51,56 +48,14 @@ class NodeGraph:
         diag = consistency(batch, ng.relative_truth(x_true))
     """
 
+    _destroy = "viekf_node_destroy"
+
     def __init__(self, batch, trail_capacity=0):
-        self._L = _bind()
-        self._h = None
-        self.batch = batch      # (the batch must outlive the node graph: it stays referenced from here)
-        self._alive()
+        super().__init__(_bind(), batch)
         self.trail_capacity = int(trail_capacity)
         h = C.c_void_p()
         capi.check(self._L.viekf_node_create(batch._h, self.trail_capacity, C.byref(h)))
         self._h = h
-
-    def _alive(self):
-        if getattr(self.batch, "_h", None) is None or not self.batch._h.value:
-            raise ValueError("the batch of this NodeGraph has been closed")
-
-    def close(self):
-        if self._h:
-            self._L.viekf_node_destroy(self._h)   # (the tables can go after their batch has)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _handle(self):
-        if not self._h:
-            raise ValueError("this NodeGraph has been closed")
-        self._alive()
-        return self._h
-
-    def _empty(self, shape, dtype, device):
-        if device:
-            import torch
-            t = torch.empty(shape, dtype=getattr(torch, np.dtype(dtype).name), device="cuda:%d" % self.batch.device)
-            return t, C.c_void_p(t.data_ptr())
-        a = np.empty(shape, dtype=dtype)
-        return a, C.c_void_p(a.ctypes.data)
-
-    def _ready(self, device, sync):
-        """device outputs come from torch's caching allocator and the inputs may still be in torch's queue, while the
-        work runs on the batch's stream (as FrameIntake does)"""
-        if device and sync:
-            import torch
-            torch.cuda.synchronize(self.batch.device)
-
-    def _done(self, device, sync):
-        if device and sync:
-            self.batch.sync()
-        self.batch._keep = []
 
     def _ldx(self, x_true):
         if len(x_true.shape) != 2:

@@ -11,6 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
+from ._dev import Handle, empty, is_torch
 
 # every symbol include/viekf_sim.h declares (tests check the library exports exactly these)
 SIM_SYMBOLS = [
@@ -55,17 +56,13 @@ def _bind():
     return L
 
 
-def _is_torch(a):
-    return hasattr(a, "data_ptr") and hasattr(a, "is_cuda")
-
-
 def landmarks_like(simulator):
     """the landmark field [L][3] of a sim.Simulator (its jitter comes from numpy's generator, which the device does not
     reproduce), for BatchSimulator.set_landmarks"""
     return np.ascontiguousarray(simulator.landmarks, dtype=np.float64)
 
 
-class BatchSimulator:
+class BatchSimulator(Handle):
     """`batch` sim.Simulator vehicles on one device.
 
         bs = BatchSimulator(B, params, max_features=8, seed=seeds, radius=radii)
@@ -79,8 +76,7 @@ class BatchSimulator:
     def __init__(self, batch, params, max_features=12, device=0, imu_rate=250.0, accel_sigma=0.3, gyro_sigma=0.01, pix_sigma=0.5,
                  grid=(-3.0, 0.22, 28), window=(15.0, 625.0, 15.0, 465.0, 0.2), seed=None, radius=None, period=None,
                  accel_bias=None, gyro_bias=None):
-        self._L = _bind()
-        self._h = None
+        super().__init__(_bind())
         self.B, self.MF, self.device = int(batch), int(max_features), int(device)
         self.params = params if isinstance(params, capi.Params) else capi.Params.from_dict(params)
         cfg = SimConfig()
@@ -98,29 +94,23 @@ class BatchSimulator:
         if any(a is not None for a in (seed, radius, period, accel_bias, gyro_bias)):
             self.set_vehicles(seed, radius, period, accel_bias, gyro_bias)
 
-    def __del__(self):
-        try:
-            if self._h:
-                self._L.viekf_sim_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
+    _destroy = "viekf_sim_destroy"
 
     # -- handle ---------------------------------------------------------------------------------------------------------
     def reset(self):
-        capi.check(self._L.viekf_sim_reset(self._h))
+        capi.check(self._L.viekf_sim_reset(self._handle()))
 
     def set_stream(self, stream):
         """a hipStream_t handle (int, e.g. torch.cuda.current_stream().cuda_stream) or None for the null stream"""
-        capi.check(self._L.viekf_sim_set_stream(self._h, None if stream is None else C.c_void_p(int(stream))))
+        capi.check(self._L.viekf_sim_set_stream(self._handle(), None if stream is None else C.c_void_p(int(stream))))
 
     def sync(self):
-        capi.check(self._L.viekf_sim_sync(self._h))
+        capi.check(self._L.viekf_sim_sync(self._handle()))
 
     @property
     def tick(self):
         k = C.c_int64()
-        capi.check(self._L.viekf_sim_dims(self._h, None, None, None, C.byref(k)))
+        capi.check(self._L.viekf_sim_dims(self._handle(), None, None, None, C.byref(k)))
         return k.value
 
     @property
@@ -140,31 +130,26 @@ class BatchSimulator:
         arrs = [self._per_vehicle(seed, np.uint64, 1), self._per_vehicle(radius, np.float64, 1), self._per_vehicle(period, np.float64, 1),
                 self._per_vehicle(accel_bias, np.float64, 3), self._per_vehicle(gyro_bias, np.float64, 3)]
         ptrs = [None if a is None else C.c_void_p(a.ctypes.data) for a in arrs]
-        capi.check(self._L.viekf_sim_set_vehicles(self._h, *ptrs, capi.HOST))
+        capi.check(self._L.viekf_sim_set_vehicles(self._handle(), *ptrs, capi.HOST))
 
     def set_landmarks(self, lm):
         """[L][3] for every vehicle or [B][L][3]; numpy or a device tensor.  Starts the simulation again."""
         per = len(lm.shape) == 3
         assert tuple(lm.shape[-2:]) == (self.L, 3) and (not per or lm.shape[0] == self.B), tuple(lm.shape)
-        if _is_torch(lm) and lm.is_cuda:
+        if is_torch(lm) and lm.is_cuda:
             import torch
             t = lm.to(torch.float64).contiguous()
             torch.cuda.synchronize(t.device)
-            capi.check(self._L.viekf_sim_set_landmarks(self._h, C.c_void_p(t.data_ptr()), int(per), capi.DEVICE))
+            capi.check(self._L.viekf_sim_set_landmarks(self._handle(), C.c_void_p(t.data_ptr()), int(per), capi.DEVICE))
             self.sync()
             return
-        a = np.ascontiguousarray(lm.numpy() if _is_torch(lm) else lm, dtype=np.float64)
-        capi.check(self._L.viekf_sim_set_landmarks(self._h, C.c_void_p(a.ctypes.data), int(per), capi.HOST))
+        a = np.ascontiguousarray(lm.numpy() if is_torch(lm) else lm, dtype=np.float64)
+        capi.check(self._L.viekf_sim_set_landmarks(self._handle(), C.c_void_p(a.ctypes.data), int(per), capi.HOST))
 
     # -- outputs --------------------------------------------------------------------------------------------------------
     def _empty(self, shape, dtype, device):
         """-> (array, pointer, where)"""
-        if device:
-            import torch
-            t = torch.empty(shape, dtype=getattr(torch, np.dtype(dtype).name), device="cuda:%d" % self.device)
-            return t, C.c_void_p(t.data_ptr()), capi.DEVICE
-        a = np.empty(shape, dtype=dtype)
-        return a, C.c_void_p(a.ctypes.data), capi.HOST
+        return empty(shape, dtype, self.device if device else None) + (capi.DEVICE if device else capi.HOST,)
 
     def _ready(self, device):
         """device outputs come from torch's caching allocator and are written on the simulator's stream: whatever torch still
@@ -181,7 +166,7 @@ class BatchSimulator:
         """Simulator.imu() at the current tick, without stepping -> [B][6]"""
         u, p, where = self._empty((self.B, 6), np.float64, device)
         self._ready(device)
-        capi.check(self._L.viekf_sim_imu(self._h, p, where))
+        capi.check(self._L.viekf_sim_imu(self._handle(), p, where))
         self._done(device)
         return u
 
@@ -189,7 +174,7 @@ class BatchSimulator:
         """K IMU periods (each _control, _step_truth, imu()) in one launch -> u [K][B][6], the `u` of BatchVIEKF.step_n"""
         u, p, where = self._empty((int(K), self.B, 6), np.float64, device)
         self._ready(device)
-        capi.check(self._L.viekf_sim_step(self._h, int(K), p, where))
+        capi.check(self._L.viekf_sim_step(self._handle(), int(K), p, where))
         self._done(device)
         return u
 
@@ -203,7 +188,7 @@ class BatchSimulator:
         dep, pd, _ = self._empty((self.B, max(N, 0)), np.float64, device)
         lm, pl, _ = self._empty((self.B, max(N, 0)), np.int32, device)
         self._ready(device)
-        capi.check(self._L.viekf_sim_camera(self._h, N, pz, pi, pc, pd, pl, where))
+        capi.check(self._L.viekf_sim_camera(self._handle(), N, pz, pi, pc, pd, pl, where))
         self._done(device)
         return z, ids, cnt, dep, lm
 
@@ -215,7 +200,7 @@ class BatchSimulator:
         if depth:
             dmm, pd, _ = self._empty((self.B, int(height), int(width)), np.float32, device)
         self._ready(device)
-        capi.check(self._L.viekf_sim_render(self._h, int(width), int(height), pi, pd, where))
+        capi.check(self._L.viekf_sim_render(self._handle(), int(width), int(height), pi, pd, where))
         self._done(device)
         return (img, dmm) if depth else img
 
@@ -224,28 +209,28 @@ class BatchSimulator:
         st, ps, where = self._empty((self.B, 13), np.float64, device)
         t, pt, _ = self._empty((self.B,), np.float64, device)
         self._ready(device)
-        capi.check(self._L.viekf_sim_get_truth(self._h, ps, pt, where))
+        capi.check(self._L.viekf_sim_get_truth(self._handle(), ps, pt, where))
         self._done(device)
         return st, t
 
     def truth_state(self, ids, device=None):
         """the true state in the filter's layout [B][17 + 5 N] for the feature slots ids [B][N] (-1 or an id that is no
         longer tracked: five NaNs), for diag.consistency(batch, x_true).  A device tensor of ids gives a device tensor."""
-        if _is_torch(ids) and ids.is_cuda:
+        if is_torch(ids) and ids.is_cuda:
             import torch
             t = ids.to(torch.int32).contiguous()
             torch.cuda.synchronize(t.device)
             N = int(t.shape[1])
             x, px, _ = self._empty((self.B, 17 + 5 * N), np.float64, True)
             self._ready(True)
-            capi.check(self._L.viekf_sim_truth_state(self._h, C.c_void_p(t.data_ptr()), N, px, capi.DEVICE))
+            capi.check(self._L.viekf_sim_truth_state(self._handle(), C.c_void_p(t.data_ptr()), N, px, capi.DEVICE))
             self.sync()
             return x
-        a = np.ascontiguousarray(ids.numpy() if _is_torch(ids) else ids, dtype=np.int32).reshape(self.B, -1)
+        a = np.ascontiguousarray(ids.numpy() if is_torch(ids) else ids, dtype=np.int32).reshape(self.B, -1)
         N = a.shape[1]
         if device:
             import torch
             return self.truth_state(torch.as_tensor(a).to("cuda:%d" % self.device))
         x = np.empty((self.B, 17 + 5 * N))
-        capi.check(self._L.viekf_sim_truth_state(self._h, C.c_void_p(a.ctypes.data) if N else None, N, C.c_void_p(x.ctypes.data), capi.HOST))
+        capi.check(self._L.viekf_sim_truth_state(self._handle(), C.c_void_p(a.ctypes.data) if N else None, N, C.c_void_p(x.ctypes.data), capi.HOST))
         return x
