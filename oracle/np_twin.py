@@ -252,19 +252,112 @@ class TwinFilter:
 
     def update_feat(self, z, R, slot, active=True):
         h, H = self.h_feat(self.x, slot)
-        res = np.asarray(z, float) - h
+        return self._correct(np.asarray(z, float) - h, H, R, active)
+
+    def _correct(self, res, H, R, active=True):
+        """vi_ekf_meas.cpp:230-271 for a residual and its Jacobian: gate, gain, NaN guard, (partial) Joseph update, fix_depth"""
+        R = np.atleast_2d(np.asarray(R, float))
         if active:
             Sinv = np.linalg.inv(H @ self.P @ H.T + R)
             if res @ Sinv @ res > 9.0:
                 return 1
             K = self.P @ H.T @ Sinv
-            I = np.eye(self.n)
-            A = I - K @ H
-            if self.partial:
-                self.x = self.boxplus(self.x, self.lam * (K @ res))
-                self.P = self.P + self.Lambda * (A @ self.P @ A.T + K @ R @ K.T - self.P)
-            else:
-                self.x = self.boxplus(self.x, K @ res)
-                self.P = A @ self.P @ A.T + K @ R @ K.T
+            if not (np.isnan(K).any() or np.isnan(H).any()):      # :247
+                I = np.eye(self.n)
+                A = I - K @ H
+                if self.partial:
+                    self.x = self.boxplus(self.x, self.lam * (K @ res))
+                    self.P = self.P + self.Lambda * (A @ self.P @ A.T + K @ R @ K.T - self.P)
+                else:
+                    self.x = self.boxplus(self.x, K @ res)
+                    self.P = A @ self.P @ A.T + K @ R @ K.T
         self.fix_depth()
         return 0
+
+    # ---- the other measurement models (vi_ekf_meas.cpp:281-386); type numbers as in the reference's enum
+    ACC, ALT, ATT, POS, VEL, QZETA, FEAT, PIXEL_VEL, DEPTH, INV_DEPTH = range(10)
+
+    def h(self, mtype, x, i=0):
+        """-> zhat, H (rdim x n) of measurement model `mtype` at x; i: the feature's local slot"""
+        n = self.n
+        if mtype == self.FEAT:
+            return self.h_feat(x, i)
+        if mtype == self.ACC:
+            if self.drag:
+                H = np.zeros((2, n))
+                H[0, 3] = H[1, 4] = -x[16]
+                H[0, 9] = H[1, 10] = 1.0
+                H[:, 15] = -x[3:5]
+                return -x[16] * x[3:5] + x[10:12], H
+            gB = Rmat(x[6:10]) @ GRAV
+            H = np.zeros((3, n))
+            H[:, 6:9] = skew(-gB)
+            H[:, 9:12] = np.eye(3)
+            return x[10:13] - gB, H
+        if mtype == self.ALT:
+            H = np.zeros((1, n))
+            H[0, 2] = -1.0
+            return np.array([-x[2]]), H
+        if mtype in (self.ATT, self.POS, self.VEL):
+            c = {self.ATT: 6, self.POS: 0, self.VEL: 3}[mtype]
+            H = np.zeros((3, n))
+            H[:, c:c + 3] = np.eye(3)
+            return (x[6:10] if mtype == self.ATT else x[c:c + 3]).copy(), H
+        if mtype == self.QZETA:
+            H = np.zeros((2, n))
+            H[:, 16 + 3 * i:18 + 3 * i] = np.eye(2)
+            return x[17 + 5 * i:21 + 5 * i].copy(), H
+        rho = x[21 + 5 * i]
+        H = np.zeros((1, n))
+        if mtype == self.DEPTH:
+            H[0, 18 + 3 * i] = -1.0 / (rho * rho)
+            return np.array([1.0 / rho]), H
+        if mtype == self.INV_DEPTH:
+            H[0, 18 + 3 * i] = 1.0
+            return np.array([rho]), H
+        raise ValueError("measurement type %d" % mtype)
+
+    def update(self, mtype, z, R, slot=0, active=True):
+        """one measurement of any model (vi_ekf_meas.cpp:196-278): residual on the manifold for ATT and QZETA (:210-217)"""
+        z = np.asarray(z, float)
+        zhat, H = self.h(mtype, self.x, slot)
+        if mtype == self.ATT:
+            res = q_boxminus(z, zhat)
+        elif mtype == self.QZETA:
+            res = q_feat_boxminus(z, zhat)
+        else:
+            res = z - zhat
+        return self._correct(res, H, R, active)
+
+    # ---- feature removal (vi_ekf_feat.cpp:50-73) and keyframe reset (vi_ekf_kfr.cpp:56-157)
+    def clear_feature(self, slot):
+        """drop the feature in local slot `slot`: the later ones move up, what is left over is zero"""
+        if not 0 <= slot < self.len:
+            return
+        xs, ds = 17 + 5 * slot, 16 + 3 * slot
+        self.x = np.concatenate([np.delete(self.x, np.s_[xs:xs + 5]), np.zeros(5)])
+        P = np.delete(np.delete(self.P, np.s_[ds:ds + 3], axis=0), np.s_[ds:ds + 3], axis=1)
+        self.P = np.zeros((self.n, self.n))
+        self.P[:self.n - 3, :self.n - 3] = P
+        self.len -= 1
+        self.x[17 + 5 * self.len:] = 0.0
+        self.P[16 + 3 * self.len:, :] = 0.0
+        self.P[:, 16 + 3 * self.len:] = 0.0
+
+    def keyframe_reset_edge(self):
+        """-> edge {t(3), q_yaw(4), cov_pos(9, column-major), cov_yaw}; position and yaw leave the state, P <- N P N^T"""
+        qw, qx, qy, qz = self.x[6:10]
+        roll = np.arctan2(2.0 * (qw * qx + qy * qz), 1.0 - 2.0 * (qx * qx + qy * qy))     # src/quat.cpp:211-224
+        pitch = np.arcsin(2.0 * (qw * qy - qz * qx))
+        yaw = np.arctan2(2.0 * (qw * qz + qx * qy), 1.0 - 2.0 * (qy * qy + qz * qz))
+        edge = np.concatenate([self.x[0:3], [np.cos(yaw / 2), 0.0, 0.0, np.sin(yaw / 2)],
+                               self.P[0:3, 0:3].ravel(order="F"), [self.P[8, 8]]])
+        self.x[0:3] = 0.0
+        cr, sr, ct, st = np.cos(roll / 2), np.sin(roll / 2), np.cos(pitch / 2), np.sin(pitch / 2)
+        self.x[6:10] = [cr * ct, sr * ct, cr * st, -sr * st]                              # from_euler(roll, pitch, 0)
+        cp, sp, tt = np.cos(roll), np.sin(roll), np.tan(pitch)
+        Nm = np.eye(self.n)
+        Nm[0:3, 0:3] = 0.0
+        Nm[6:9, 6:9] = [[1.0, sp * tt, cp * tt], [0.0, cp * cp, -cp * sp], [0.0, -cp * sp, sp * sp]]   # :134-142
+        self.P = Nm @ self.P @ Nm.T
+        return edge
