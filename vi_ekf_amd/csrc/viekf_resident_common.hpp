@@ -115,10 +115,18 @@ __device__ __forceinline__ double uniform_f64(double v) {   // force a wave-unif
 }
 
 // Diagnostic build only (-DVIEKF_STAMPS): s_memtime stamps of block 0 into the (otherwise unused) workspace.
+// (-DVIEKF_STAMPS=2 keeps only the per-wave stamps of one update, 192 .. 223: thread 0's per-update stamps are then not in wave 0's
+//  instruction stream -- an s_memtime in flight turns that wave's counted LDS waits into full drains, NOTES A (xix) -- and the three
+//  worker waves run the same code)
 #ifdef VIEKF_STAMPS
+#if VIEKF_STAMPS + 0 == 2
+#define RES_STAMP_KEPT(idx) ((idx) >= 192 && (idx) < 224)
+#else
+#define RES_STAMP_KEPT(idx) true
+#endif
 #define RES_STAMP(S_, who, idx)                                                                  \
   do {                                                                                           \
-    if ((S_).b == 0 && (who)) {                                                                  \
+    if (RES_STAMP_KEPT(idx) && (S_).b == 0 && (who)) {                                                                  \
       __builtin_amdgcn_sched_barrier(0);                                                         \
       reinterpret_cast<unsigned long long*>((S_).stamps)[(idx)] = __builtin_amdgcn_s_memtime();  \
       __builtin_amdgcn_sched_barrier(0);                                                         \
@@ -186,6 +194,22 @@ constexpr bool res_batched_loads(int RB, int NW) { return NW != 7 && RB != 8; }
 // stream it had before.
 constexpr bool res_setup_under_load(int RB, int NW, bool MP) {
   return res_batched_loads(RB, NW) && !MP && ((NW == 3 && (RB == 4 || RB == 6 || RB == 7)) || (NW == 6 && RB == 5));
+}
+// Which kernels ROTATE the operand reads of their sweeps under the multiply-adds (res_worker), a mask of parts:
+//   1  the update loop's block sweep: two operand buffers, block ia + 2's rows of K and W are read into the buffer block ia's
+//      multiply-adds just released -- L(0) L(1) F(0) L(2) F(1) ... F(RB - 1) -- instead of two blocks' reads, a wait, their
+//      multiply-adds and a fence, four times per update at RB = 7.  A gated or NaN-guarded update reads no operand
+//   2  the propagate's K = 24 contraction, the same order inside a trip k
+// Only instances with more than four blocks per thread have groups to rotate (RB <= 4 holds every operand in flight at once); all
+// seven of them take both parts, in every flavour: no launch of theirs timed slower beyond its spread, none gained a spill
+// (profiles/rotating_reads/instances_ab.md, budget.md) -- the arguments beyond RB are there for an instance that has to be gated off.
+// VIEKF_ROTATING_READS masks the parts at build time (tools/build_variant.sh parent_order -DVIEKF_ROTATING_READS=0 builds the
+// old order from this tree); a kernel whose mask is 0 compiles to the instruction stream it had before.
+#ifndef VIEKF_ROTATING_READS
+#define VIEKF_ROTATING_READS 3
+#endif
+constexpr int res_rotating_reads(int RB, int NW, bool MP, bool ZU) {
+  return (RB > 4) ? ((VIEKF_ROTATING_READS) & 3) : 0;
 }
 // false = not owned (then I = J = 0: every LDS / global read stays in range, results are never stored)
 __device__ __forceinline__ bool res_word_blk(int e, int& I, int& J) {

@@ -134,6 +134,7 @@ __device__ __forceinline__ void res_body_items(const ResShared& S, const double*
 template <int RB, int TW, bool MP, int T = TW + 64, bool ZU = false, bool BL = true>
 __device__ __forceinline__ void res_worker(const StreamArgs& a, const ResShared& S, int tid) {
   constexpr bool SU = res_setup_under_load(RB, TW / 64, MP);
+  constexpr int RR = res_rotating_reads(RB, TW / 64, MP, ZU);   // parts: 1 update-loop sweep, 2 contraction
   const int N = S.N, n = S.n, ld = a.ld, nf = S.nf, len = S.len;
   double* P = a.P + S.si * n * ld;
   // SYMMETRIC ownership: of each unordered pair of feature blocks {I,J} only one is kept (I >= J); which thread keeps it in
@@ -394,6 +395,43 @@ __device__ __forceinline__ void res_worker(const StreamArgs& a, const ResShared&
     }
     auto contract = [&](int k, auto crossed) {
       constexpr bool CROSS = decltype(crossed)::value;
+      if (RR & 2) {   // rotated (res_rotating_reads): the records of block ia + 2 are read under the multiply-adds of block ia + 1
+        double2 xb[2][3], yb[2][3];
+#pragma unroll
+        for (int ia = 0; ia < 2; ia++) {
+          const double* zi = Z + (zoff[ia] & 0xffff) + 2 * k;
+          const double* zj = Z + (zoff[ia] >> 16) + 2 * k;
+#pragma unroll
+          for (int r = 0; r < 3; r++) xb[ia][r] = lds_ld2(zi + r * ZS);
+#pragma unroll
+          for (int s = 0; s < 3; s++) yb[ia][s] = lds_ld2(zj + s * ZS);
+        }
+#pragma unroll
+        for (int ia = 0; ia < RB; ia++) {
+          const int ib = ia & 1;
+#pragma unroll
+          for (int r = 0; r < 3; r++)
+#pragma unroll
+            for (int s = 0; s < 3; s++) {
+              double acc = pb[ia][r * 3 + s];
+              acc = fma(xb[ib][r].x, CROSS ? yb[ib][s].y : yb[ib][s].x, acc);
+              acc = fma(xb[ib][r].y, CROSS ? yb[ib][s].x : yb[ib][s].y, acc);
+              pb[ia][r * 3 + s] = acc;
+            }
+          group_fence<true>();
+          if (ia + 2 < RB) {
+            constexpr int RBL = RB - 1;
+            const int in = (ia + 2 < RB) ? ia + 2 : RBL;
+            const double* zi = Z + (zoff[in] & 0xffff) + 2 * k;
+            const double* zj = Z + (zoff[in] >> 16) + 2 * k;
+#pragma unroll
+            for (int r = 0; r < 3; r++) xb[ib][r] = lds_ld2(zi + r * ZS);
+#pragma unroll
+            for (int s = 0; s < 3; s++) yb[ib][s] = lds_ld2(zj + s * ZS);
+          }
+        }
+        return;
+      }
 #pragma unroll
       for (int ia = 0; ia < RB; ia++) {
         const double* zi = Z + (zoff[ia] & 0xffff) + 2 * k;
@@ -556,6 +594,46 @@ __device__ __forceinline__ void res_worker(const StreamArgs& a, const ResShared&
     const bool gated = gflag != 0.0;
     const bool run = !gated && nanw == 0.0 && !RES_ABLATE(S, 1);   // not gated, no NaN guard
     bool fixed = false;
+    if (RR & 1) {
+      // rotated (res_rotating_reads): L(0) L(1) F(0) L(2) F(1) ... F(RB - 1), L(i) the six operand reads of block i into buffer
+      // i & 1, F(i) its multiply-adds.  LDS reads return in order, so F(i) waits for L(i) with L(i + 1) still in flight.  The fix
+      // comes first, as it did (ahead of the first multiply-add on pb[0][8]); an update that does not run reads nothing.
+      apply_fixes(par ^ 1, fixpending);
+      if (run) {
+        double2 kb[2][3], wb[2][3];
+#pragma unroll
+        for (int ia = 0; ia < 2; ia++) {
+#pragma unroll
+          for (int r = 0; r < 3; r++) kb[ia][r] = lds_ld2(kP + 2 * (16 + 3 * Ib[ia] + r));
+#pragma unroll
+          for (int s = 0; s < 3; s++) wb[ia][s] = lds_ld2(wP + 2 * (16 + 3 * Jb[ia] + s));
+        }
+#pragma unroll
+        for (int ia = 0; ia < RB; ia++) {
+          const int ib = ia & 1;
+#pragma unroll
+          for (int r = 0; r < 3; r++)
+#pragma unroll
+            for (int s = 0; s < 3; s++) {
+              if (ZU && !(r == 2 && s == 2)) {   // Lambda = 1: two multiply-adds instead of three operations
+                pb[ia][r * 3 + s] = fma(-kb[ib][r].y, wb[ib][s].y, fma(-kb[ib][r].x, wb[ib][s].x, pb[ia][r * 3 + s]));
+              } else {
+                const double t = fma(kb[ib][r].y, wb[ib][s].y, kb[ib][r].x * wb[ib][s].x);
+                pb[ia][r * 3 + s] = fma(-Lff[r * 3 + s], t, pb[ia][r * 3 + s]);
+              }
+            }
+          group_fence<true>();
+          if (ia + 2 < RB) {
+            constexpr int RBL = RB - 1;
+            const int in = (ia + 2 < RB) ? ia + 2 : RBL;
+#pragma unroll
+            for (int r = 0; r < 3; r++) kb[ib][r] = lds_ld2(kP + 2 * (16 + 3 * Ib[in] + r));
+#pragma unroll
+            for (int s = 0; s < 3; s++) wb[ib][s] = lds_ld2(wP + 2 * (16 + 3 * Jb[in] + s));
+          }
+        }
+      }
+    } else
 #pragma unroll
     for (int g0 = 0; g0 < RB; g0 += GB) {
       double2 kI[GB][3], wJ[GB][3];
