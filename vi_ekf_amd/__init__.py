@@ -16,3 +16,5 @@ from . import frame  # noqa: E402,F401
 from .frame import FrameIntake  # noqa: E402,F401
 from . import node  # noqa: E402,F401
 from .node import NodeGraph  # noqa: E402,F401
+from . import map  # noqa: E402,F401
+from .map import LandmarkMap  # noqa: E402,F401
