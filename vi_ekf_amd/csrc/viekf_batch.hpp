@@ -1,6 +1,7 @@
 // viekf_batch.hpp -- the batch handle of the C ABI (include/viekf.h) and the handle's small accessors (the error plumbing and
 // the owner of its device memory are viekf_hostkit.hpp).
-// Pulls in viekf_kernels_stream.hpp (StreamArgs), which defines kernels: for the one HIP translation unit, viekf_capi.hip.
+// Of the device side it needs the kernel arguments only (viekf_kernel_args.hpp: StreamArgs, no kernel defined there).  HIP
+// host code all the same (hipStream_t, the owner's hipMalloc): part of viekf_capi.hip's translation unit.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,7 +12,7 @@
 
 #include "../../include/viekf.h"
 #include "viekf_hostkit.hpp"
-#include "viekf_kernels_stream.hpp"
+#include "viekf_kernel_args.hpp"
 #include "viekf_pform.hpp"
 
 using namespace viekf;

@@ -489,8 +489,7 @@ int viekf_batch_keep_features(viekf_batch* b, const uint8_t* keep, int32_t* new_
   Staged st(b, where);
   if (int rc = st.begin(in(keep, BN, &d_keep), out(new_len, (size_t)b->B, &d_nl))) return rc;
   StreamArgs a = make_args(b);
-  const size_t lds = sizeof(double) * (size_t)b->n + sizeof(int) * (size_t)(b->n + 4);
-  hipLaunchKernelGGL(k_keep_features<kThreads>, dim3(b->B), dim3(kThreads), lds, b->stream, a, d_keep, d_nl);
+  hipLaunchKernelGGL(k_keep_features<kThreads>, dim3(b->B), dim3(kThreads), KeepLds(b->n).bytes(), b->stream, a, d_keep, d_nl);
   HIP_TRY(hipGetLastError());
   return st.finish();
 }
@@ -519,8 +518,7 @@ int viekf_batch_eval_xdot(viekf_batch* b, const double* u, double* xdot, viekf_m
   Staged st(b, where);
   if (int rc = st.begin(in(u, 6 * (size_t)b->B, &d_u), out(xdot, (size_t)b->B * b->n, &d_o))) return rc;
   StreamArgs a = make_args(b);
-  const size_t lds = sizeof(double) * (size_t)(b->nxs + 256 + 96 + 16) + sizeof(BodyCtx) + 16;
-  hipLaunchKernelGGL(k_eval_xdot<kThreads>, dim3(b->B), dim3(kThreads), lds, b->stream, a, d_u, d_o);
+  hipLaunchKernelGGL(k_eval_xdot<kThreads>, dim3(b->B), dim3(kThreads), XdotLds(b->nxs, sizeof(BodyCtx)).bytes(), b->stream, a, d_u, d_o);
   HIP_TRY(hipGetLastError());
   return st.finish();
 }
@@ -987,9 +985,8 @@ int viekf_batch_update(viekf_batch* b, int32_t type, const double* z, int32_t zd
                         out(result, B, &d_res)))
     return rc;
   StreamArgs a = make_args(b);
-  const size_t lds = sizeof(double) * (size_t)(b->nxs + 7 * b->n + 64);
-  hipLaunchKernelGGL(k_update_generic<kThreads>, dim3(b->B), dim3(kThreads), lds, b->stream, a, type, zdim, rdim, d_z,
-                     d_slot, d_R, r_mode ? (long)rr : 0L, d_act, d_res);
+  hipLaunchKernelGGL(k_update_generic<kThreads>, dim3(b->B), dim3(kThreads), GenLds(b->nxs, b->n).bytes(), b->stream, a, type, zdim,
+                     rdim, d_z, d_slot, d_R, r_mode ? (long)rr : 0L, d_act, d_res);
   HIP_TRY(hipGetLastError());
   return st.finish();
 }

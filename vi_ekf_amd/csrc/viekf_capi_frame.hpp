@@ -185,8 +185,7 @@ int viekf_frame_intake(viekf_frame* f, int32_t M, const double* z, const int32_t
   hipLaunchKernelGGL(k_frame_plan, dim3(b->B), dim3(64), plds, b->stream, a, t, M, d_z, d_ids, d_depth, d_R, r_mode, d_act, use_kfr,
                      b->params.keyframe_overlap_threshold, d_edges);
   HIP_TRY(hipGetLastError());
-  const size_t klds = sizeof(double) * (size_t)b->n + sizeof(int) * (size_t)(b->n + 4);
-  hipLaunchKernelGGL(k_keep_features<kThreads>, dim3(b->B), dim3(kThreads), klds, b->stream, a, t.keep, nullptr);
+  hipLaunchKernelGGL(k_keep_features<kThreads>, dim3(b->B), dim3(kThreads), KeepLds(b->n).bytes(), b->stream, a, t.keep, nullptr);
   HIP_TRY(hipGetLastError());
   if (use_kfr) {
     hipLaunchKernelGGL(k_keyframe_reset<kThreads>, dim3(b->B), dim3(kThreads), 0, b->stream, a, t.rmask, d_edges);

@@ -136,6 +136,58 @@ VD void body_boxplus(const double* x, const double* dx, double* o) {
   for (int i = 0; i < 7; i++) o[xB_A + i] = x[xB_A + i] + dx[dxB_A + i];
 }
 
+// ---- the minus side of the manifold: log, boxminus of a quaternion / a bearing / the state, the yaw of an attitude
+__device__ __forceinline__ void q_log_dev(const double* q, double* o) {   // src/quat.cpp:82-98
+  const double nv = sqrt(q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+  if (nv < 1e-8) { o[0] = o[1] = o[2] = 0.0; }
+  else { const double s = 2.0 * atan2(nv, q[0]) / nv; o[0] = s * q[1]; o[1] = s * q[2]; o[2] = s * q[3]; }
+}
+__device__ __forceinline__ void q_boxminus_dev(const double* q1, const double* q2, double* o) {   // src/quat.cpp:319-327
+  const double inv[4] = {q2[0], -q2[1], -q2[2], -q2[3]};
+  double dq[4];
+  q_otimes(inv, q1, dq);
+  if (dq[0] < 0.0) { dq[0] = -dq[0]; dq[1] = -dq[1]; dq[2] = -dq[2]; dq[3] = -dq[3]; }
+  q_log_dev(dq, o);
+}
+__device__ __forceinline__ void q_feat_boxminus_dev(const double* qj, const double* qi, double* o) {   // math_helper.h:25-43
+  double t1[3], t2[3], zi[3], a1[3], a2[3], zj[3];
+  bearing_frame(qi, t1, t2, zi);
+  bearing_frame(qj, a1, a2, zj);
+  const double d[3] = {zi[0] - zj[0], zi[1] - zj[1], zi[2] - zj[2]};
+  if (sqrt(dot3(d, d)) > 1e-8) {
+    double s[3];
+    cross3(zi, zj, s);
+    const double ns = sqrt(dot3(s, s));
+    const double th = acos(dot3(zi, zj));
+    s[0] = s[0] / ns * th; s[1] = s[1] / ns * th; s[2] = s[2] / ns * th;
+    o[0] = dot3(t1, s); o[1] = dot3(t2, s);
+  } else { o[0] = 0.0; o[1] = 0.0; }
+}
+
+// x1 [-] x2 of the body state into o[0..15] and of one feature into o3[0..2] (vi_ekf_helper.cpp:100-111)
+__device__ __forceinline__ void body_boxminus_dev(const double* x1, const double* x2, double* o) {
+  for (int i = 0; i < 6; i++) o[dxPOS + i] = x1[xPOS + i] - x2[xPOS + i];
+  double d3[3];
+  q_boxminus_dev(x1 + xATT, x2 + xATT, d3);
+  for (int i = 0; i < 3; i++) o[dxATT + i] = d3[i];
+  for (int i = 0; i < 7; i++) o[dxB_A + i] = x1[xB_A + i] - x2[xB_A + i];
+}
+__device__ __forceinline__ void feat_boxminus_dev(const double* f1, const double* f2, double* o3) {
+  q_feat_boxminus_dev(f1, f2, o3);
+  o3[2] = f1[4] - f2[4];
+}
+
+// The yaw part of an attitude, as the reset takes it out of the state and hands it to the node frame: stated once, for the
+// edge of k_keyframe_reset (viekf_kernels_lifecycle.hpp) and for the node graph's true node (viekf_kernels_node.hpp), which
+// applies the same map to the truth.
+__device__ __forceinline__ double q_yaw_dev(const double* q) {                             // src/quat.cpp:221-224
+  const double qw = q[0], qx = q[1], qy = q[2], qz = q[3];
+  return atan2(2.0 * (qw * qz + qx * qy), 1.0 - 2.0 * (qy * qy + qz * qz));
+}
+__device__ __forceinline__ void q_from_yaw_dev(double yaw, double* o) {                   // from_euler(0,0,yaw), :150-165
+  o[0] = cos(yaw / 2.0); o[1] = 0.0; o[2] = 0.0; o[3] = sin(yaw / 2.0);
+}
+
 // Quantities of the body state shared by the body and every feature block (vi_ekf_dyn.cpp:27-39, 83-94).
 struct BodyCtx {
   double vel[3], omega[3], acc[3], mu;

@@ -1,6 +1,8 @@
 // viekf_dispatch.hpp -- which kernel runs a batch and how it is launched: the instance tables, the choice of an instance when a
-// batch is created (setup_resident / setup_tiles), the launches of the three families.  Included by viekf_capi.hip ONLY: the
-// kernel headers below define non-template __global__ functions, a second includer would define them twice.
+// batch is created (setup_resident / setup_tiles), the launches of the three families.  The headers that DEFINE kernels are
+// included here (and the companions' from viekf_capi.hip), nowhere else; what several of them share -- the kernel arguments,
+// the measurement models, the LDS layouts -- defines none.  So a new kernel, template or not, needs no guard: the objects of
+// viekf_inst.hip include viekf_instances.hpp alone, which reaches no header with a non-template __global__.
 #pragma once
 #include <cstdlib>
 #include <initializer_list>
@@ -8,7 +10,11 @@
 
 #include "viekf_batch.hpp"
 #include "viekf_instances.hpp"
+#include "viekf_kernels_generic.hpp"
 #include "viekf_kernels_hooks.hpp"
+#include "viekf_kernels_lifecycle.hpp"
+#include "viekf_kernels_stream.hpp"
+#include "viekf_kernels_util.hpp"
 #include "viekf_kernels_wide.hpp"
 
 // (the fused-step kernels are compiled in viekf_inst.hip, one object file per group of instances)
@@ -47,11 +53,6 @@ void r_strides(int r_mode, int M, long* rsb, long* rsm) {
   *rsm = r_mode == 2 ? 4 : 0;
 }
 
-size_t lds_propagate(const viekf_batch* b) {
-  return sizeof(double) * (size_t)(b->nxs + 256 + 96 + 256 + 256 + 96 + 256 + 256 + 16) + sizeof(BodyCtx) + 16;
-}
-size_t lds_update(const viekf_batch* b) { return sizeof(double) * (size_t)(b->nxs + 5 * b->n + 32); }
-
 // A grouped update (k_update_feat_blocked) keeps only the lower triangle of P current; the matrix-core propagate reads only
 // that and rewrites all of P; a fused launch may leave P packed.  Every reader says which form it can take: require_P, below
 // the kernel tables.
@@ -70,13 +71,13 @@ int launch_propagate(viekf_batch* b, const double* d_u, const double* d_dt, cons
       if (int rc = raise_dyn_lds({&k_propagate_wide<512>}, wlds, have[b->device & 63])) return rc;
       hipLaunchKernelGGL((k_propagate_wide<512>), dim3(b->B), dim3(512), wlds, b->stream, a, d_u, d_dt);
     } else {                                                                    // r02's K = 38 form, operands staged in global scratch
-      hipLaunchKernelGGL((k_propagate_stream<512, true>), dim3(b->B), dim3(512), lds_propagate(b) + sizeof(double) * (9 * (size_t)b->N + 2),
+      hipLaunchKernelGGL((k_propagate_stream<512, true>), dim3(b->B), dim3(512), PropLds(b->nxs, sizeof(BodyCtx), b->N, true).bytes(),
                          b->stream, a, d_u, d_dt);
     }
     b->book.wrote_live(PForm::Lower);
   } else
-    hipLaunchKernelGGL((k_propagate_stream<kThreads, false>), dim3(b->B), dim3(kThreads), lds_propagate(b), b->stream, a, d_u,
-                       d_dt);
+    hipLaunchKernelGGL((k_propagate_stream<kThreads, false>), dim3(b->B), dim3(kThreads),
+                       PropLds(b->nxs, sizeof(BodyCtx), b->N, false).bytes(), b->stream, a, d_u, d_dt);
   HIP_TRY(hipGetLastError());
   return VIEKF_OK;
 }
@@ -133,8 +134,8 @@ int launch_update(viekf_batch* b, const double* d_z, const int* d_slot, int M, c
     b->book.wrote_live(PForm::Lower);   // (reads and writes the lower triangle only)
   } else {
     if (int rc = require_P(b, PForm::Full)) return rc;   // (the one-measurement kernel reads whole columns)
-    hipLaunchKernelGGL(k_update_feat_stream<kThreads>, dim3(b->B), dim3(kThreads), lds_update(b), b->stream, a, d_z,
-                       d_slot, M, d_R, rsb, rsm, d_res);
+    hipLaunchKernelGGL(k_update_feat_stream<kThreads>, dim3(b->B), dim3(kThreads), UpdLds(b->nxs, b->n).bytes(), b->stream, a,
+                       d_z, d_slot, M, d_R, rsb, rsm, d_res);
   }
   HIP_TRY(hipGetLastError());
   return VIEKF_OK;

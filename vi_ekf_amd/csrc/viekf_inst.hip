@@ -1,6 +1,5 @@
 // viekf_inst.hip -- explicit instantiations of the fused-step kernels of group VIEKF_INST_GROUP (viekf_instances.hpp).
 #include <hip/hip_runtime.h>
-#define VIEKF_INSTANCES_ONLY
 #include "viekf_instances.hpp"
 
 #define RES_DEF(...) VIEKF_RES_FLAVOURS(, __VA_ARGS__)

@@ -18,7 +18,8 @@
 //             columns are 16 and T/16 apart, so that the lanes of a wave read 16 consecutive doubles of a panel column
 //             (the others broadcast): 8 LDS reads per 16 FMAs.
 #pragma once
-#include "viekf_kernels_stream.hpp"
+#include "viekf_kernel_args.hpp"
+#include "viekf_meas_models.hpp"
 
 namespace viekf {
 
@@ -136,7 +137,6 @@ __device__ __forceinline__ int dg_factor(double* __restrict__ A, const int m) {
   return info;
 }
 
-#ifndef VIEKF_INSTANCES_ONLY
 // Filters b0 + blockIdx.x.  LDS: the packed triangle lives in dynamic LDS (diag_packed_doubles(n) doubles); otherwise in
 // ws + blockIdx.x * ws_stride.  x_true [B][nx] or NULL (then e = 0); every output may be NULL.
 template <int T, bool LDS>
@@ -276,6 +276,5 @@ __global__ __launch_bounds__(64) void k_diag_innovation(StreamArgs a, int type, 
   if (S_out)
     for (int i = 0; i < 9; i++) S_out[e * 9 + i] = S[i];
 }
-#endif
 
 }  // namespace viekf

@@ -15,7 +15,7 @@
 // Between them run the existing k_keep_features, k_keyframe_reset and the batch's own FEAT update.  Synchronisation is
 // __syncthreads() and wave intrinsics only: no flags, tickets or polling between waves, nothing here can wait for ever.
 #pragma once
-#include "viekf_kernels_stream.hpp"
+#include "viekf_kernel_args.hpp"
 
 namespace viekf {
 

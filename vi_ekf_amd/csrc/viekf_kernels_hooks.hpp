@@ -5,12 +5,77 @@
 // jac_test properties (test/jac_test.cpp:245-487) and the symbolic Jacobians can be checked against DEVICE output.  They use the
 // same device functions as the hot kernels (body_dynamics, feature_dynamics, meas_model, body_boxplus, q_feat_boxplus ...).
 // None of them changes a filter; the state they evaluate at is an explicit argument (NULL = the batch's current state).
+// With them the read-only evaluations of the log writer (k_eval_xdot, k_eval_h), at the batch's current state.
+// Defines kernels: included from viekf_dispatch.hpp only.
 #pragma once
-#include "viekf_kernels_stream.hpp"
+#include "viekf_kernel_args.hpp"
+#include "viekf_meas_models.hpp"
+#include "viekf_stream_lds.hpp"
 
 namespace viekf {
 
-#ifndef VIEKF_INSTANCES_ONLY
+// ------------------------------------------------------------------------------------------------
+// Read-only evaluations for the log writer (src/vi_ekf/vi_ekf_log.cpp): what the reference records next to a propagate
+// (xdot = dx_ of VIEKF::dynamics, vi_ekf_dyn.cpp:6-134; the diagonal of P) and next to an update (zhat = h(x),
+// vi_ekf_meas.cpp:281-386).  They do not touch the filter, so the hot kernels carry no logging arguments.
+// ------------------------------------------------------------------------------------------------
+template <int T>
+__global__ __launch_bounds__(T) void k_eval_xdot(StreamArgs a, const double* __restrict__ u_all, double* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  if (b >= a.B) return;
+  const XdotLds lds(a.nxs, sizeof(BodyCtx));
+  double* xs = smem + lds.xs;
+  double* Abb = smem + lds.Abb;
+  double* Gb = smem + lds.Gb;
+  double* xdb = smem + lds.xdb;
+  BodyCtx* ctx = reinterpret_cast<BodyCtx*>(smem + lds.ctx);
+  const int len = a.len[b];
+  const double* xg = a.x + a.si(b) * a.nxs;
+  for (int i = tid; i < xZ + 5 * len; i += T) xs[i] = xg[i];
+  __syncthreads();
+  if (tid == 0) {
+    double ub[6];
+    q_rota(a.dp->q_b_u, u_all + (long)b * 6, ub);          // vi_ekf.cpp:265-267
+    q_rota(a.dp->q_b_u, u_all + (long)b * 6 + 3, ub + 3);
+    body_ctx(xs, ub, (*a.dp), *ctx);
+    body_dynamics(*ctx, (*a.dp), xdb, Abb, Gb);
+  }
+  __syncthreads();
+  double* o = out + (long)b * a.n;
+  for (int i = tid; i < a.n; i += T) {
+    double v = 0.0;
+    if (i < 16) v = xdb[i];
+    else {
+      const int f = (i - 16) / 3, q = (i - 16) - 3 * f;
+      if (f < len) {
+        double xd3[3], Afv[9], Afg[9], Aff[9];
+        feature_dynamics(xs + xZ + 5 * f, xs[xZ + 5 * f + 4], *ctx, xd3, Afv, Afg, Aff);
+        v = xd3[q];
+      }
+    }
+    o[i] = v;
+  }
+}
+
+// zhat [B][4] of measurement model `type` at the current state (one thread per filter); unused entries and filters whose
+// slot is out of range get NaN
+__global__ void k_eval_h(StreamArgs a, int type, const int* __restrict__ slot_all, double* __restrict__ out) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= a.B) return;
+  const double* xs = a.x + a.si(b) * a.nxs;
+  const DevParams& prm = *a.dp;
+  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+  double zhat[4] = {nan, nan, nan, nan};
+  const bool needs_slot = meas_needs_slot(type);
+  const int slot = (needs_slot && slot_all) ? slot_all[b] : 0;
+  if (!needs_slot || (slot >= 0 && slot < a.len[b])) {   // (meas_model writes only the entries its model uses)
+    int cols[6], nc; double Hc[18];
+    meas_model(type, xs, slot, prm, zhat, cols, Hc, nc);
+  }
+  for (int i = 0; i < 4; i++) out[(long)b * 4 + i] = zhat[i];
+}
+
 // dynamics(x, u, xdot, dfdx, dfdu): u is the body-frame input, as that overload takes it (NOT rotated by q_b_u: propagate_state
 // does that before it calls dynamics, vi_ekf.cpp:265-267,295).  xdot [B][n], A [B][n][n], G [B][6][n] (column-major n x n / n x 6),
 // everything the reference leaves zero is zero.  One workgroup per filter; x_in [B][nx] or NULL.
@@ -65,7 +130,7 @@ __global__ void k_eval_H(StreamArgs a, const double* __restrict__ x_in, int type
   const double* xs = x_in ? x_in + (long)b * a.nx : a.x + a.si(b) * a.nxs;
   double* H = H_out + (long)b * n * 3;
   for (int e = 0; e < 3 * n; e++) H[e] = 0.0;
-  const bool needs_slot = type == MT_QZETA || type == MT_FEAT || type == MT_DEPTH || type == MT_INV_DEPTH;
+  const bool needs_slot = meas_needs_slot(type);
   const int slot = (needs_slot && slot_all) ? slot_all[b] : 0;
   const double nan = __longlong_as_double(0x7ff8000000000000LL);
   double zhat[4] = {0.0, 0.0, 0.0, 0.0};
@@ -150,6 +215,5 @@ __global__ __launch_bounds__(256) void k_eval_reset(StreamArgs a, const double* 
     }
   }
 }
-#endif
 
 }  // namespace viekf

@@ -15,7 +15,7 @@
 // synchronisation between waves, every loop unrolled over constant bounds so that the small matrices stay in registers (no
 // scratch).  Lane -> work: ONE LANE PER FILTER, all 21 loads of P issued before the first use (DESIGN.md §13 says why).
 #pragma once
-#include "viekf_kernels_stream.hpp"
+#include "viekf_kernel_args.hpp"
 
 namespace viekf {
 

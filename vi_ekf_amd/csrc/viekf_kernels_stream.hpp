@@ -9,81 +9,18 @@
 //   H of a FEAT measurement has one 2x2 block (vi_ekf_meas.cpp:366) => W = P H^T is two columns of P and
 //      (I-KH)P(I-KH)^T + KRK^T - P = -K W^T, so the partial update (vi_ekf_meas.cpp:254-257) is
 //      P_ij -= Lambda_ij (K_i . W_j),  Lambda_ij = l_i + l_j - l_i l_j  (vi_ekf.cpp:83,146).
+//
+// Defines kernels: included from viekf_dispatch.hpp only.  The kernel arguments are viekf_kernel_args.hpp, the dynamic-LDS
+// carve-ups of k_propagate_stream and k_update_feat_stream viekf_stream_lds.hpp (BlkLds, the grouped update's, is below).
 #pragma once
-#include "viekf_device.hpp"
-#include "viekf_fastmath.hpp"
+#include "viekf_kernel_args.hpp"
+#include "viekf_stream_lds.hpp"
 
 namespace viekf {
-
-struct StreamArgs {
-  double* x;            // [B][nxs]
-  double* P;            // [B][n][ld]
-  int* len;             // [B]
-  unsigned* flags;      // [B]
-  const double* Qx;     // [n] diagonal
-  const double* lambda; // [n]
-  double* ws;           // [B][ws_stride]
-  int B, N, nx, nxs, n, ld;
-  long ws_stride;
-  const DevParams* dp;  // device memory (uniform loads); NOT by value: indexing a by-value kernarg array spills it to scratch
-  double* x_out;        // where the fused-step kernel stores the state / covariance: the same buffers (in place) or another
-  double* P_out;        // slot of the history ring (viekf_batch_propagate_to: the propagate writes the NEXT slot, no copy)
-  const unsigned char* active;   // [B] or NULL: filters with active[b] == 0 take no part in a propagate / feature-update launch
-                                 // (viekf_batch_set_active: filters on different clocks share a batch)
-  const int* resmap;    // fused-step kernel: ownership map of the 3x3 feature blocks, [RB][TW] entries I | J << 8 | owned << 16
-  // Per-filter live ring slots (viekf_batch_select_filters: filters on clocks of their own share a batch, each with its own ring
-  // position): x / P then point at the RING, [slot][B] entries, and filter b's state is entry smap[b] = slot_b * B + b of it.
-  // smap_out: where the fused kernel stores filter b's state (viekf_batch_propagate_filters_to: slot i_b -> slot i_b + 1, no copy).
-  int* smap;            // (device memory; the fused kernel moves a filter's entry to smap_out[b] when it stores it there)
-  const int* smap_out;
-  // [B] or NULL: propagates of THIS launch per filter (viekf_batch_propagate_n_filters_to; >= 1 for every filter that takes part).
-  // Read by the multi-propagate instances of the fused kernel only; NULL = the launch-wide count of the launch word.
-  const int* kcount;
-  __device__ __forceinline__ long si(int b) const { return smap ? (long)smap[b] : (long)b; }
-  __device__ __forceinline__ long so(int b) const { return smap_out ? (long)smap_out[b] : si(b); }
-};
-
-constexpr int WK = 40;   // contraction depth of the low-rank part (16 + 16 + 6, padded to whole MFMA k-steps of 4)
-typedef double v4f64 __attribute__((ext_vector_type(4)));
-
-// workspace carve-up (doubles) for one filter
-struct WsLayout {
-  long phi_fb, phi_ff, gd, U, pbr, pbc, Xw, Yw, total;
-  __host__ __device__ WsLayout(int N, int n) {
-    long o = 0;
-    phi_fb = o; o += 3L * N * 16;   // [3N][16]
-    phi_ff = o; o += 9L * N;        // [N][9]
-    gd = o;     o += 6L * n;        // [n][6]
-    U = o;      o += 3L * N * 16;   // [3N][16]   (Phi P)[feat rows, body cols]
-    pbr = o;    o += 16L * n;       // [16][n]    copy of P[body rows, :]
-    pbc = o;    o += 16L * n;       // [16][n]    copy of P[:, body cols], stored [k][i]
-    const long nfp = ((3L * N + 47) / 48) * 48;
-    Xw = o;     o += nfp * WK;      // [nfp][WK]  low-rank factors of the propagate's MFMA pass (k_propagate_stream<.., true>):
-    Yw = o;     o += nfp * WK;      //            P+_ff = D P_ff D^T + Xw Yw^T, rows padded to whole 48-row super-tiles
-    total = (o + 1) & ~1L;
-  }
-};
-
-// fix_depth (vi_ekf_helper.cpp:128-156) for feature i of the block's filter; xs is the LDS copy of x
-__device__ __forceinline__ void fix_depth_one(double* xs, double* P, int ld, int i, const DevParams& p, unsigned& flag) {
-  const int xR = xZ + 5 * i + 4, dR = dxZ + 3 * i + 2;
-  double rho = xs[xR];
-  fix_depth_rule(rho, 1.0 / (2.0 * p.min_depth), flag, [&](double e2) { P[dR + (long)dR * ld] += e2; },
-                 [&] { P[dR + (long)dR * ld] = p.P0_feat[2]; });
-  xs[xR] = rho;
-}
 
 // ------------------------------------------------------------------------------------------------
 // propagate: numeric core of VIEKF::propagate_state (vi_ekf.cpp:262-318)
 // ------------------------------------------------------------------------------------------------
-// LDS written by some lanes of a wave and read by others of the SAME wave: order the accesses (the compiler treats lanes as
-// independent threads and may otherwise move the loads above the stores)
-__device__ __forceinline__ void wave_lds_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // MF = true: the feature/feature part runs on the fp64 matrix cores (see the pass at the end); otherwise one 3x3 block per thread.
 template <int T, bool MF>
 __global__ __launch_bounds__(T) void k_propagate_stream(StreamArgs a, const double* __restrict__ u_all,
@@ -93,17 +30,18 @@ __global__ __launch_bounds__(T) void k_propagate_stream(StreamArgs a, const doub
   if (b >= a.B) return;
   if (a.active && !a.active[b]) return;
   const int n = a.n, ld = a.ld;
-  double* xs = smem;                    // [nxs]
-  double* Abb = xs + a.nxs;             // 16x16 row-major
-  double* Gb = Abb + 256;               // 16x6
-  double* Phibb = Gb + 96;              // 16x16
-  double* Mbb = Phibb + 256;            // 16x16
-  double* Gdb = Mbb + 256;              // 16x6
-  double* Pbb = Gdb + 96;               // 16x16 row-major copy of P_bb
-  double* T16 = Pbb + 256;              // 16x16 scratch
-  double* xdb = T16 + 256;              // 16
-  BodyCtx* ctx = reinterpret_cast<BodyCtx*>(xdb + 16);
-  double* Dl = xdb + 16 + (sizeof(BodyCtx) + 7) / 8;   // [N][9] Phi_ff blocks (MF only)
+  const PropLds lds(a.nxs, sizeof(BodyCtx), a.N, MF);
+  double* xs = smem + lds.xs;           // [nxs]
+  double* Abb = smem + lds.Abb;         // 16x16 row-major
+  double* Gb = smem + lds.Gb;           // 16x6
+  double* Phibb = smem + lds.Phibb;     // 16x16
+  double* Mbb = smem + lds.Mbb;         // 16x16
+  double* Gdb = smem + lds.Gdb;         // 16x6
+  double* Pbb = smem + lds.Pbb;         // 16x16 row-major copy of P_bb
+  double* T16 = smem + lds.T16;         // 16x16 scratch
+  double* xdb = smem + lds.xdb;         // 16
+  BodyCtx* ctx = reinterpret_cast<BodyCtx*>(smem + lds.ctx);
+  double* Dl = smem + lds.Dl;           // [N][9] Phi_ff blocks (MF only)
 
   double* xg = a.x + a.si(b) * a.nxs;
   double* P = a.P + a.si(b) * n * ld;
@@ -440,11 +378,12 @@ __global__ __launch_bounds__(T) void k_update_feat_stream(StreamArgs a, const do
   if (b >= a.B) return;
   if (a.active && !a.active[b]) return;
   const int n = a.n, ld = a.ld;
-  double* xs = smem;           // [nxs]
-  double* W = xs + a.nxs;      // [n][2]
-  double* K = W + 2 * n;       // [n][2]
-  double* lam = K + 2 * n;     // [n]
-  double* sm = lam + n;        // small scratch: zhat(2) Hb(4) res(2) Sinv(4) = 12, dxb(16)
+  const UpdLds lds(a.nxs, n);
+  double* xs = smem + lds.xs;     // [nxs]
+  double* W = smem + lds.W;       // [n][2]
+  double* K = smem + lds.K;       // [n][2]
+  double* lam = smem + lds.lam;   // [n]
+  double* sm = smem + lds.sm;     // small scratch: zhat(2) Hb(4) res(2) Sinv(4) = 12, dxb(16)
   double* xg = a.x + a.si(b) * a.nxs;
   double* P = a.P + a.si(b) * n * ld;
   const int len = a.len[b];
@@ -951,608 +890,5 @@ __global__ __launch_bounds__(T) void k_update_feat_blocked(StreamArgs a, const d
   }
   if (flag) atomicOr(&a.flags[b], flag);
 }
-
-// ------------------------------------------------------------------------------------------------
-// generic measurement update: VIEKF::update for every measurement model of the reference's table
-// (vi_ekf_meas.cpp:196-278 with h_acc/h_alt/h_att/h_pos/h_vel/h_qzeta/h_feat/h_depth/h_inv_depth, :281-386).
-// Each H has at most 6 non-zero columns, so W = P H^T is a combination of <= 6 columns of P and the update is the same
-// rank-r sweep  P_ij -= Lambda_ij (K_i . W_j)  as for FEAT.  One workgroup per filter, P in HBM/L2 (these models run at
-// IMU / truth rate, one per propagate -- not the N-per-frame hot loop).
-// ------------------------------------------------------------------------------------------------
-constexpr int MT_ACC = 0, MT_ALT = 1, MT_ATT = 2, MT_POS = 3, MT_VEL = 4, MT_QZETA = 5, MT_FEAT = 6, MT_DEPTH = 8,
-              MT_INV_DEPTH = 9;   // include/vi_ekf.h:113-124
-
-__device__ __forceinline__ void q_log_dev(const double* q, double* o) {   // src/quat.cpp:82-98
-  const double nv = sqrt(q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-  if (nv < 1e-8) { o[0] = o[1] = o[2] = 0.0; }
-  else { const double s = 2.0 * atan2(nv, q[0]) / nv; o[0] = s * q[1]; o[1] = s * q[2]; o[2] = s * q[3]; }
-}
-__device__ __forceinline__ void q_boxminus_dev(const double* q1, const double* q2, double* o) {   // src/quat.cpp:319-327
-  const double inv[4] = {q2[0], -q2[1], -q2[2], -q2[3]};
-  double dq[4];
-  q_otimes(inv, q1, dq);
-  if (dq[0] < 0.0) { dq[0] = -dq[0]; dq[1] = -dq[1]; dq[2] = -dq[2]; dq[3] = -dq[3]; }
-  q_log_dev(dq, o);
-}
-__device__ __forceinline__ void q_feat_boxminus_dev(const double* qj, const double* qi, double* o) {   // math_helper.h:25-43
-  double t1[3], t2[3], zi[3], a1[3], a2[3], zj[3];
-  bearing_frame(qi, t1, t2, zi);
-  bearing_frame(qj, a1, a2, zj);
-  const double d[3] = {zi[0] - zj[0], zi[1] - zj[1], zi[2] - zj[2]};
-  if (sqrt(dot3(d, d)) > 1e-8) {
-    double s[3];
-    cross3(zi, zj, s);
-    const double ns = sqrt(dot3(s, s));
-    const double th = acos(dot3(zi, zj));
-    s[0] = s[0] / ns * th; s[1] = s[1] / ns * th; s[2] = s[2] / ns * th;
-    o[0] = dot3(t1, s); o[1] = dot3(t2, s);
-  } else { o[0] = 0.0; o[1] = 0.0; }
-}
-// r x r inverse (r <= 3) by LU with partial pivoting, row-major (Eigen's dynamic-size inverse, vi_ekf_meas.cpp:232)
-__device__ __forceinline__ void small_inverse_dev(int r, const double* S, double* Si) {
-  double a[9], b[9];
-  for (int i = 0; i < r; i++) for (int j = 0; j < r; j++) { a[i * 3 + j] = S[i * r + j]; b[i * 3 + j] = (i == j) ? 1.0 : 0.0; }
-  for (int c = 0; c < r; c++) {
-    int piv = c; double best = fabs(a[c * 3 + c]);
-    for (int i = c + 1; i < r; i++) if (fabs(a[i * 3 + c]) > best) { best = fabs(a[i * 3 + c]); piv = i; }
-    if (piv != c) for (int j = 0; j < r; j++) {
-      double t = a[c * 3 + j]; a[c * 3 + j] = a[piv * 3 + j]; a[piv * 3 + j] = t;
-      t = b[c * 3 + j]; b[c * 3 + j] = b[piv * 3 + j]; b[piv * 3 + j] = t;
-    }
-    for (int i = c + 1; i < r; i++) {
-      const double l = a[i * 3 + c] / a[c * 3 + c];
-      for (int j = 0; j < r; j++) { a[i * 3 + j] -= l * a[c * 3 + j]; b[i * 3 + j] -= l * b[c * 3 + j]; }
-    }
-  }
-  for (int j = 0; j < r; j++)
-    for (int i = r - 1; i >= 0; i--) {
-      double s = b[i * 3 + j];
-      for (int k = i + 1; k < r; k++) s -= a[i * 3 + k] * Si[k * r + j];
-      Si[i * r + j] = s / a[i * 3 + i];
-    }
-}
-
-// the models that measure a feature: they take a feature slot (QZETA, FEAT, DEPTH, INV_DEPTH)
-__device__ __forceinline__ bool meas_needs_slot(int type) {
-  return type == MT_QZETA || type == MT_FEAT || type == MT_DEPTH || type == MT_INV_DEPTH;
-}
-
-// The reference's measurement models (src/vi_ekf/vi_ekf_meas.cpp:281-386): zhat = h(x) and the non-zero columns of H -- at most six
-// (`cols`, their number `nc`), Hc [3][6] row-major = the entries of H in those columns.  One lane; xs = the filter's state.
-__device__ __forceinline__ void meas_model(int type, const double* xs, int slot, const DevParams& prm, double* zhat, int* cols,
-                                           double* Hc, int& nc) {
-  nc = 0;
-  for (int i = 0; i < 18; i++) Hc[i] = 0.0;
-  auto col = [&](int c) { cols[nc] = c; return nc++; };
-  if (type == MT_ACC) {                                       // vi_ekf_meas.cpp:281-306
-    if (prm.use_drag_term) {
-      const double mu = xs[xMU];
-      zhat[0] = -mu * xs[xVEL] + xs[xB_A]; zhat[1] = -mu * xs[xVEL + 1] + xs[xB_A + 1];
-      int c;
-      c = col(dxVEL); Hc[0 * 6 + c] = -mu;  c = col(dxVEL + 1); Hc[1 * 6 + c] = -mu;
-      c = col(dxB_A); Hc[0 * 6 + c] = 1.0;  c = col(dxB_A + 1); Hc[1 * 6 + c] = 1.0;
-      c = col(dxMU); Hc[0 * 6 + c] = -xs[xVEL]; Hc[1 * 6 + c] = -xs[xVEL + 1];
-    } else {
-      const double g[3] = {0.0, 0.0, kGravity}; double gB[3], ng[3], Sk[9];
-      q_rotp(xs + xATT, g, gB);
-      for (int i = 0; i < 3; i++) { zhat[i] = xs[xB_A + i] - gB[i]; ng[i] = -1.0 * gB[i]; }
-      skew3(ng, Sk);
-      for (int j = 0; j < 3; j++) { const int c = col(dxATT + j); for (int i = 0; i < 3; i++) Hc[i * 6 + c] = Sk[i * 3 + j]; }
-      for (int j = 0; j < 3; j++) { const int c = col(dxB_A + j); Hc[j * 6 + c] = 1.0; }
-    }
-  } else if (type == MT_ALT) { zhat[0] = -xs[xPOS + 2]; const int c = col(dxPOS + 2); Hc[c] = -1.0; }
-  else if (type == MT_ATT) { for (int i = 0; i < 4; i++) zhat[i] = xs[xATT + i]; for (int j = 0; j < 3; j++) { const int c = col(dxATT + j); Hc[j * 6 + c] = 1.0; } }
-  else if (type == MT_POS) { for (int j = 0; j < 3; j++) { zhat[j] = xs[xPOS + j]; const int c = col(dxPOS + j); Hc[j * 6 + c] = 1.0; } }
-  else if (type == MT_VEL) { for (int j = 0; j < 3; j++) { zhat[j] = xs[xVEL + j]; const int c = col(dxVEL + j); Hc[j * 6 + c] = 1.0; } }
-  else if (type == MT_QZETA) { for (int i = 0; i < 4; i++) zhat[i] = xs[xZ + 5 * slot + i]; for (int j = 0; j < 2; j++) { const int c = col(dxZ + 3 * slot + j); Hc[j * 6 + c] = 1.0; } }
-  else if (type == MT_FEAT) {
-    double Hb[4]; h_feat(xs + xZ + 5 * slot, prm, zhat, Hb);
-    for (int j = 0; j < 2; j++) { const int c = col(dxZ + 3 * slot + j); Hc[0 * 6 + c] = Hb[0 * 2 + j]; Hc[1 * 6 + c] = Hb[1 * 2 + j]; }
-  } else if (type == MT_DEPTH) { const double rho = xs[xZ + 5 * slot + 4]; zhat[0] = 1.0 / rho; const int c = col(dxZ + 3 * slot + 2); Hc[c] = -1.0 / (rho * rho); }
-  else if (type == MT_INV_DEPTH) { zhat[0] = xs[xZ + 5 * slot + 4]; const int c = col(dxZ + 3 * slot + 2); Hc[c] = 1.0; }
-}
-
-// residual z [-] zhat of a model (vi_ekf_meas.cpp:209-220): a quaternion measurement by its boxminus, the others subtract
-__device__ __forceinline__ void meas_residual(int type, const double* z, const double* zhat, int zdim, double* r3) {
-  if (type == MT_QZETA) q_feat_boxminus_dev(z, zhat, r3);           // :210-213
-  else if (type == MT_ATT) q_boxminus_dev(z, zhat, r3);             // :214-217
-  else for (int i = 0; i < zdim && i < 3; i++) r3[i] = z[i] - zhat[i];
-}
-
-// x1 [-] x2 of the body state into o[0..15] and of one feature into o3[0..2] (vi_ekf_helper.cpp:100-111)
-__device__ __forceinline__ void body_boxminus_dev(const double* x1, const double* x2, double* o) {
-  for (int i = 0; i < 6; i++) o[dxPOS + i] = x1[xPOS + i] - x2[xPOS + i];
-  double d3[3];
-  q_boxminus_dev(x1 + xATT, x2 + xATT, d3);
-  for (int i = 0; i < 3; i++) o[dxATT + i] = d3[i];
-  for (int i = 0; i < 7; i++) o[dxB_A + i] = x1[xB_A + i] - x2[xB_A + i];
-}
-__device__ __forceinline__ void feat_boxminus_dev(const double* f1, const double* f2, double* o3) {
-  q_feat_boxminus_dev(f1, f2, o3);
-  o3[2] = f1[4] - f2[4];
-}
-
-// ------------------------------------------------------------------------------------------------
-// Read-only evaluations for the log writer (src/vi_ekf/vi_ekf_log.cpp): what the reference records next to a propagate
-// (xdot = dx_ of VIEKF::dynamics, vi_ekf_dyn.cpp:6-134; the diagonal of P) and next to an update (zhat = h(x),
-// vi_ekf_meas.cpp:281-386).  They do not touch the filter, so the hot kernels carry no logging arguments.
-// ------------------------------------------------------------------------------------------------
-template <int T>
-__global__ __launch_bounds__(T) void k_eval_xdot(StreamArgs a, const double* __restrict__ u_all, double* __restrict__ out) {
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  if (b >= a.B) return;
-  double* xs = smem;
-  double* Abb = xs + a.nxs;
-  double* Gb = Abb + 256;
-  double* xdb = Gb + 96;
-  BodyCtx* ctx = reinterpret_cast<BodyCtx*>(xdb + 16);
-  const int len = a.len[b];
-  const double* xg = a.x + a.si(b) * a.nxs;
-  for (int i = tid; i < xZ + 5 * len; i += T) xs[i] = xg[i];
-  __syncthreads();
-  if (tid == 0) {
-    double ub[6];
-    q_rota(a.dp->q_b_u, u_all + (long)b * 6, ub);          // vi_ekf.cpp:265-267
-    q_rota(a.dp->q_b_u, u_all + (long)b * 6 + 3, ub + 3);
-    body_ctx(xs, ub, (*a.dp), *ctx);
-    body_dynamics(*ctx, (*a.dp), xdb, Abb, Gb);
-  }
-  __syncthreads();
-  double* o = out + (long)b * a.n;
-  for (int i = tid; i < a.n; i += T) {
-    double v = 0.0;
-    if (i < 16) v = xdb[i];
-    else {
-      const int f = (i - 16) / 3, q = (i - 16) - 3 * f;
-      if (f < len) {
-        double xd3[3], Afv[9], Afg[9], Aff[9];
-        feature_dynamics(xs + xZ + 5 * f, xs[xZ + 5 * f + 4], *ctx, xd3, Afv, Afg, Aff);
-        v = xd3[q];
-      }
-    }
-    o[i] = v;
-  }
-}
-
-// zhat [B][4] of measurement model `type` at the current state (one thread per filter); unused entries and filters whose
-// slot is out of range get NaN
-#ifndef VIEKF_INSTANCES_ONLY
-__global__ void k_eval_h(StreamArgs a, int type, const int* __restrict__ slot_all, double* __restrict__ out) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= a.B) return;
-  const double* xs = a.x + a.si(b) * a.nxs;
-  const DevParams& prm = *a.dp;
-  const double nan = __longlong_as_double(0x7ff8000000000000LL);
-  double zhat[4] = {nan, nan, nan, nan};
-  const bool needs_slot = meas_needs_slot(type);
-  const int slot = (needs_slot && slot_all) ? slot_all[b] : 0;
-  if (!needs_slot || (slot >= 0 && slot < a.len[b])) {   // (meas_model writes only the entries its model uses)
-    int cols[6], nc; double Hc[18];
-    meas_model(type, xs, slot, prm, zhat, cols, Hc, nc);
-  }
-  for (int i = 0; i < 4; i++) out[(long)b * 4 + i] = zhat[i];
-}
-#endif
-
-// P <- (P + P^T) / 2 of every filter (a covariance handed in through viekf_batch_set_state): the kernels keep P exactly
-// symmetric from then on and rely on it.  A NaN in the active block of the P handed in raises VIEKF_FLAG_NAN: the kernels only
-// test x for NaN, and the reference's NaNsInTheHouse (vi_ekf_error.cpp:6-18) tests P as well.
-#ifndef VIEKF_INSTANCES_ONLY
-__global__ void k_symmetrize(StreamArgs a) {
-  const int b = blockIdx.y;
-  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= a.B || e >= (long)a.n * a.n) return;
-  const int i = (int)(e % a.n), j = (int)(e / a.n);
-  if (i < j) return;
-  double* P = a.P + a.si(b) * a.n * a.ld;
-  const double v = i == j ? P[i + (long)i * a.ld] : 0.5 * (P[i + (long)j * a.ld] + P[j + (long)i * a.ld]);
-  if (i > j) {
-    P[i + (long)j * a.ld] = v;
-    P[j + (long)i * a.ld] = v;
-  }
-  if (v != v && i < dxZ + 3 * a.len[b]) atomicOr(&a.flags[b], FLAG_NAN);
-}
-#endif
-
-// upper triangle <- lower triangle (bit for bit), 32 x 32 tiles through LDS so that both sides are coalesced along the rows.
-// Runs when a grouped update left the upper triangle stale (k_update_feat_blocked) and something is about to read all of P.
-#ifndef VIEKF_INSTANCES_ONLY
-__global__ __launch_bounds__(256) void k_mirror_upper(StreamArgs a) {
-  __shared__ double t[32][33];
-  const int b = blockIdx.y, n = a.n, nt = (n + 31) >> 5;
-  // tile pairs (ti >= tj) numbered row by row: blockIdx.x = ti (ti + 1) / 2 + tj
-  int ti = (int)((sqrtf(1.0f + 8.0f * (float)blockIdx.x) - 1.0f) * 0.5f);
-  while (ti * (ti + 1) / 2 > (int)blockIdx.x) ti--;
-  while ((ti + 1) * (ti + 2) / 2 <= (int)blockIdx.x) ti++;
-  const int tj = (int)blockIdx.x - ti * (ti + 1) / 2;
-  if (ti >= nt) return;
-  double* P = a.P + a.si(b) * n * a.ld;
-  const int lx = threadIdx.x & 31, ly = threadIdx.x >> 5;
-  for (int c = ly; c < 32; c += 8) {
-    const int i = 32 * ti + lx, j = 32 * tj + c;
-    t[c][lx] = (i < n && j < n) ? P[i + (long)j * a.ld] : 0.0;
-  }
-  __syncthreads();
-  for (int c = ly; c < 32; c += 8) {
-    const int i = 32 * tj + lx, j = 32 * ti + c;     // destination element (i, j) = source element (j, i)
-    if (i < n && j < n && i < j) P[i + (long)j * a.ld] = t[lx][c];   // (a diagonal tile: its strictly upper part only)
-  }
-}
-#endif
-
-#ifndef VIEKF_INSTANCES_ONLY
-__global__ void k_cov_diag(StreamArgs a, double* __restrict__ out) {
-  const int b = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b < a.B && i < a.n) out[(long)b * a.n + i] = a.P[a.si(b) * a.n * a.ld + i + (long)i * a.ld];
-}
-#endif
-
-// per-filter history: copies (x, P) of filter b between the batch's live buffers and ring slot slot[b] (< 0: filter skipped);
-// to_ring != 0: live -> ring.  Filters on independent clocks advance and rewind their rings separately (viekf_seq, independent
-// mode); the feature counts are not part of a slot, as in the reference's ring (include/vi_ekf.h:156-160).
-#ifndef VIEKF_INSTANCES_ONLY
-__global__ __launch_bounds__(256) void k_ring_copy(StreamArgs a, double* __restrict__ ring_x, double* __restrict__ ring_P,
-                                                   const int* __restrict__ slot, int to_ring, int depth) {
-  const int b = blockIdx.x;
-  if (b >= a.B) return;
-  const int sl = slot[b];
-  if (sl < 0) return;
-  if (sl >= depth) {   // (a device-resident slot list cannot be validated by the host: nothing is copied, the filter is flagged)
-    if (threadIdx.x == 0) atomicOr(&a.flags[b], FLAG_INTERNAL);
-    return;
-  }
-  const long nP = (long)a.n * a.ld;
-  double* lx = a.x + a.si(b) * a.nxs;
-  double* lP = a.P + a.si(b) * nP;
-  double* rx = ring_x + ((long)sl * a.B + b) * a.nxs;
-  double* rP = ring_P + ((long)sl * a.B + b) * nP;
-  const double2* src = reinterpret_cast<const double2*>(to_ring ? lP : rP);   // (ld is even and the buffers 16-byte aligned)
-  double2* dst = reinterpret_cast<double2*>(to_ring ? rP : lP);
-  for (long e = threadIdx.x; e < nP / 2; e += 256) dst[e] = src[e];
-  for (int e = threadIdx.x; e < a.nxs; e += 256) (to_ring ? rx : lx)[e] = (to_ring ? lx : rx)[e];
-}
-#endif
-
-// per-filter live slots: smap[b] = slot[b] * B + b for the filters with slot[b] >= 0 (viekf_batch_select_filters: the rewind of
-// filters on clocks of their own is this index, vi_ekf_meas.cpp:50-52 per filter)
-#ifndef VIEKF_INSTANCES_ONLY
-__global__ __launch_bounds__(256) void k_set_smap(int* __restrict__ smap, const int* __restrict__ slot, int B) {
-  const int b = blockIdx.x * 256 + threadIdx.x;
-  if (b < B && slot[b] >= 0) smap[b] = slot[b] * B + b;
-}
-#endif
-
-// a rectangular block P[r0 .. r0+nr, c0 .. c0+nc) of every filter -> out [B][nc][nr] (column-major per filter)
-#ifndef VIEKF_INSTANCES_ONLY
-__global__ void k_cov_block(StreamArgs a, int r0, int c0, int nr, int nc, double* __restrict__ out) {
-  const int b = blockIdx.y, e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= a.B || e >= nr * nc) return;
-  const int c = e / nr, r = e - c * nr;
-  out[(long)b * nr * nc + e] = a.P[a.si(b) * a.n * a.ld + (r0 + r) + (long)(c0 + c) * a.ld];
-}
-#endif
-
-template <int T>
-__global__ __launch_bounds__(T) void k_update_generic(StreamArgs a, int type, int zdim, int rdim,
-                                                      const double* __restrict__ z_all, const int* __restrict__ slot_all,
-                                                      const double* __restrict__ R_all, long r_stride_b,
-                                                      const unsigned char* __restrict__ active_all,
-                                                      int* __restrict__ result_all) {
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  if (b >= a.B) return;
-  const int n = a.n, ld = a.ld;
-  const DevParams& prm = *a.dp;
-  double* xs = smem;            // [nxs]
-  double* W = xs + a.nxs;       // [n][3]
-  double* K = W + 3 * n;        // [n][3]
-  double* lam = K + 3 * n;      // [n]
-  double* sm = lam + n;         // [64]: hcols (int as double) [0..5], Hc [6..23] (3 rows x 6 cols), res [24..26], ncol [27], Si [28..36], verdict [37]
-  double* xg = a.x + a.si(b) * a.nxs;
-  double* P = a.P + a.si(b) * n * ld;
-  const int len = a.len[b];
-  const int nact = 16 + 3 * len;
-  const int slot = slot_all ? slot_all[b] : 0;
-  const bool active = active_all ? active_all[b] != 0 : true;
-  int* res_out = result_all ? &result_all[b] : nullptr;
-  if (active_all && active_all[b] == 2) { if (res_out && tid == 0) *res_out = -1; return; }   // this filter skips the call
-  unsigned flag = 0;
-  if (meas_needs_slot(type) && (slot < 0 || slot >= len)) { if (res_out && tid == 0) *res_out = (slot < 0) ? -1 : 3; return; }
-  const double* z = z_all + (long)b * zdim;
-  {
-    bool isnan_ = false;
-    for (int i = 0; i < zdim; i++) isnan_ |= z[i] != z[i];
-    if (isnan_) { if (res_out && tid == 0) *res_out = 2; return; }   // MEAS_NAN
-  }
-  for (int i = tid; i < xZ + 5 * len; i += T) xs[i] = xg[i];
-  for (int i = tid; i < n; i += T) lam[i] = a.lambda[i];
-  __syncthreads();
-
-  if (tid == 0) {   // measurement model: zhat, the non-zero columns of H, residual
-    int cols[6]; double Hc[18]; int nc = 0; double zhat[4] = {0, 0, 0, 0}; double r3[3] = {0, 0, 0};
-    meas_model(type, xs, slot, prm, zhat, cols, Hc, nc);
-    meas_residual(type, z, zhat, zdim, r3);
-    for (int i = 0; i < 6; i++) sm[i] = (i < nc) ? (double)cols[i] : 0.0;
-    for (int i = 0; i < 18; i++) sm[6 + i] = Hc[i];
-    sm[24] = r3[0]; sm[25] = r3[1]; sm[26] = r3[2]; sm[27] = (double)nc;
-  }
-  __syncthreads();
-  if (!active) {   // :230 -- an inactive measurement only runs fix_depth (and the logger)
-    for (int f = tid; f < len; f += T) fix_depth_one(xs, P, ld, f, prm, flag);
-    __syncthreads();
-    for (int i = tid; i < xZ + 5 * len; i += T) xg[i] = xs[i];
-    if (res_out && tid == 0) *res_out = 0;
-    if (flag) atomicOr(&a.flags[b], flag);
-    return;
-  }
-  const int nc = (int)sm[27];
-  // W = P H^T  (n x r): combination of the nc non-zero columns
-  for (int i = tid; i < nact; i += T) {
-    double w[3] = {0.0, 0.0, 0.0};
-    for (int c = 0; c < nc; c++) {
-      const double pv = P[i + (long)((int)sm[c]) * ld];
-      for (int q = 0; q < rdim; q++) w[q] += pv * sm[6 + q * 6 + c];
-    }
-    for (int q = 0; q < 3; q++) W[3 * i + q] = w[q];
-  }
-  __syncthreads();
-  if (tid == 0) {   // S = H W[cols] + R, inverse, gate
-    const double* R = R_all + (long)b * r_stride_b;   // column-major rdim x rdim
-    double S[9], Si[9];
-    for (int p = 0; p < rdim; p++)
-      for (int q = 0; q < rdim; q++) {
-        double s = 0.0;
-        for (int c = 0; c < nc; c++) s += sm[6 + p * 6 + c] * W[3 * (int)sm[c] + q];
-        S[p * rdim + q] = s + R[p + q * rdim];
-      }
-    small_inverse_dev(rdim, S, Si);
-    double mahal = 0.0;
-    for (int q = 0; q < rdim; q++) { double t = 0.0; for (int p = 0; p < rdim; p++) t += sm[24 + p] * Si[p * rdim + q]; mahal += t * sm[24 + q]; }
-    for (int i = 0; i < 9; i++) sm[28 + i] = (i < rdim * rdim) ? Si[i] : 0.0;
-    sm[37] = (mahal > kGateMahal) ? 1.0 : 0.0;   // :234-239
-  }
-  __syncthreads();
-  if (sm[37] != 0.0) { if (res_out && tid == 0) *res_out = 1; return; }   // gated: returns before fix_depth
-  int bad = 0;
-  for (int i = tid; i < nact; i += T) {
-    for (int q = 0; q < 3; q++) {
-      double k = 0.0;
-      if (q < rdim) for (int p = 0; p < rdim; p++) k += W[3 * i + p] * sm[28 + p * rdim + q];
-      K[3 * i + q] = k;
-      if (k != k) bad = 1;
-    }
-  }
-  for (int i = 0; i < 18; i++) if (sm[6 + i] != sm[6 + i]) bad = 1;
-  bad = __syncthreads_or(bad);
-  if (!bad) {
-    const bool partial = prm.use_partial_update != 0;
-    if (tid == 0) {
-      double dxb[16], xo[17];
-      for (int i = 0; i < 16; i++) {
-        const double l = partial ? lam[i] : 1.0;
-        double s = 0.0;
-        for (int q = 0; q < rdim; q++) s += (l * K[3 * i + q]) * sm[24 + q];
-        dxb[i] = s;
-      }
-      body_boxplus(xs, dxb, xo);
-      for (int i = 0; i < 17; i++) xs[i] = xo[i];
-    }
-    for (int f = tid; f < len; f += T) {
-      const int d = 16 + 3 * f;
-      double dv[3];
-      for (int e = 0; e < 3; e++) {
-        const double l = partial ? lam[d + e] : 1.0;
-        double s = 0.0;
-        for (int q = 0; q < rdim; q++) s += (l * K[3 * (d + e) + q]) * sm[24 + q];
-        dv[e] = s;
-      }
-      double qn[4];
-      q_feat_boxplus(xs + xZ + 5 * f, dv[0], dv[1], qn);
-      double* xf = xs + xZ + 5 * f;
-      xf[0] = qn[0]; xf[1] = qn[1]; xf[2] = qn[2]; xf[3] = qn[3];
-      xf[4] += dv[2];
-    }
-    const long tot = (long)nact * nact;
-    for (long e = tid; e < tot; e += T) {
-      const int i = (int)(e % nact), j = (int)(e / nact);
-      const int hi = max(i, j), lo = min(i, j);   // (exactly symmetric result, see k_update_feat_stream)
-      double t = 0.0;
-      for (int q = 0; q < rdim; q++) t += K[3 * hi + q] * W[3 * lo + q];
-      const double li = lam[i], lj = lam[j];
-      const double L = partial ? (lj + li - li * lj) : 1.0;
-      P[i + (long)j * ld] -= L * t;
-    }
-  }
-  __syncthreads();
-  for (int f = tid; f < len; f += T) fix_depth_one(xs, P, ld, f, prm, flag);
-  __syncthreads();
-  for (int i = tid; i < xZ + 5 * len; i += T) {
-    const double v = xs[i];
-    if (v != v) flag |= FLAG_NAN;
-    if (v > 1e6) flag |= FLAG_BLOWUP;
-    xg[i] = v;
-  }
-  if (res_out && tid == 0) *res_out = 0;
-  if (flag) atomicOr(&a.flags[b], flag);
-}
-
-// ------------------------------------------------------------------------------------------------
-// init_feature (vi_ekf_feat.cpp:6-47), one workgroup per filter
-// ------------------------------------------------------------------------------------------------
-template <int T>
-__global__ __launch_bounds__(T) void k_init_feature(StreamArgs a, const double* __restrict__ pix_all,
-                                                    const double* __restrict__ depth_all,
-                                                    const unsigned char* __restrict__ mask, int* __restrict__ ok) {
-  const int b = blockIdx.x, tid = threadIdx.x;
-  if (b >= a.B) return;
-  if (mask && !mask[b]) { if (ok && tid == 0) ok[b] = 0; return; }
-  const int len = a.len[b];
-  if (len >= a.N) { if (ok && tid == 0) ok[b] = 0; return; }   // :9-10
-  const int n = a.n, ld = a.ld;
-  double* P = a.P + a.si(b) * n * ld;
-  const int d0 = 16 + 3 * len, dmax = d0 + 3;
-  if (tid == 0) {
-    double q[4], rho;
-    init_feature_state(pix_all + 2L * b, depth_all ? depth_all[b] : NAN, (*a.dp), q, &rho);
-    double* xf = a.x + a.si(b) * a.nxs + xZ + 5 * len;
-    xf[0] = q[0]; xf[1] = q[1]; xf[2] = q[2]; xf[3] = q[3]; xf[4] = rho;
-  }
-  // zero the cross strips, set the 3x3 block to P0_feat (:39-42)
-  for (int e = tid; e < 3 * d0; e += T) {
-    const int j = e / 3, r = e % 3;
-    P[(d0 + r) + (long)j * ld] = 0.0;
-    P[j + (long)(d0 + r) * ld] = 0.0;
-  }
-  if (tid < 9) {
-    const int r = tid % 3, c = tid / 3;
-    P[(d0 + r) + (long)(d0 + c) * ld] = (r == c) ? a.dp->P0_feat[r] : 0.0;
-  }
-  (void)dmax;
-  __syncthreads();
-  if (tid == 0) {
-    a.len[b] = len + 1;
-    if (ok) ok[b] = 1;
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// keep_only_features / clear_feature (vi_ekf_feat.cpp:50-73,81-117): drop the features whose keep flag is 0 and shift the
-// survivors (state and covariance rows/columns) to the upper-left corner, zeroing what is left over.  One workgroup per
-// filter; columns are moved through an LDS buffer in increasing order, so the in-place compaction never overwrites a
-// column that is still needed.  (The keyframe-overlap bookkeeping of keep_only_features stays on the host.)
-// ------------------------------------------------------------------------------------------------
-template <int T>
-__global__ __launch_bounds__(T) void k_keep_features(StreamArgs a, const unsigned char* __restrict__ keep_all,
-                                                     int* __restrict__ new_len) {
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  if (b >= a.B) return;
-  const int n = a.n, ld = a.ld, N = a.N;
-  double* colbuf = smem;                                   // [n]
-  int* srcrow = reinterpret_cast<int*>(smem + n);          // [n] old row index of new row i (or -1)
-  int* cnt = srcrow + n;
-  double* xg = a.x + a.si(b) * a.nxs;
-  double* P = a.P + a.si(b) * n * ld;
-  const int len = a.len[b];
-  const unsigned char* keep = keep_all + (long)b * N;
-  if (tid == 0) {
-    for (int i = 0; i < 16; i++) srcrow[i] = i;
-    int k = 0;
-    for (int f = 0; f < len; f++)
-      if (keep[f]) { for (int q = 0; q < 3; q++) srcrow[16 + 3 * k + q] = 16 + 3 * f + q; k++; }
-    for (int i = 16 + 3 * k; i < n; i++) srcrow[i] = -1;
-    *cnt = k;
-  }
-  __syncthreads();
-  const int k = *cnt;
-  if (k == len) { if (new_len && tid == 0) new_len[b] = len; return; }   // nothing to drop
-  // state: features are 5 doubles each
-  if (tid == 0) {
-    int w = 0;
-    for (int f = 0; f < len; f++)
-      if (keep[f]) { if (w != f) for (int q = 0; q < 5; q++) xg[xZ + 5 * w + q] = xg[xZ + 5 * f + q]; w++; }
-    for (int i = xZ + 5 * k; i < xZ + 5 * N; i++) xg[i] = 0.0;   // "clean up the rest" (vi_ekf_feat.cpp:66-69): EVERYTHING past the
-  }                                                              // kept features, also what a replay from older history left there
-  const int nk = 16 + 3 * k, nold = n;
-  for (int jn = 0; jn < nold; jn++) {
-    const int jo = (jn < nk) ? srcrow[jn] : -1;
-    if (jo >= 0) for (int i = tid; i < nk; i += T) colbuf[i] = P[srcrow[i] + (long)jo * ld];
-    __syncthreads();
-    for (int i = tid; i < nold; i += T) P[i + (long)jn * ld] = (jo >= 0 && i < nk) ? colbuf[i] : 0.0;
-    __syncthreads();
-  }
-  if (tid == 0) { a.len[b] = k; if (new_len) new_len[b] = k; }
-}
-
-// ------------------------------------------------------------------------------------------------
-// keyframe reset ("Dan's way", vi_ekf_kfr.cpp:56-157): position <- 0, yaw <- 0, P <- N P N^T where N differs from I only
-// in the position block (0) and the attitude block (RMEKF Eq. 81).  One workgroup per filter, in place: first the row
-// operation N P (every thread owns columns), then the column operation (every thread owns rows).  edge [B][17] (optional):
-// {t(3), q_yaw(4), cov_pos(9, column-major), cov_yaw} of the relative pose before the reset, for the caller's global-pose
-// bookkeeping (:58-62,125-126,147-149 -- the Xformd algebra of the reference's `geometry` dependency stays with the caller).
-// ------------------------------------------------------------------------------------------------
-// The yaw part of an attitude, as the reset takes it out of the state and hands it to the node frame: stated once, for the
-// edge below and for the node graph's true node (viekf_kernels_node.hpp), which applies the same map to the truth.
-__device__ __forceinline__ double q_yaw_dev(const double* q) {                             // src/quat.cpp:221-224
-  const double qw = q[0], qx = q[1], qy = q[2], qz = q[3];
-  return atan2(2.0 * (qw * qz + qx * qy), 1.0 - 2.0 * (qy * qy + qz * qz));
-}
-__device__ __forceinline__ void q_from_yaw_dev(double yaw, double* o) {                   // from_euler(0,0,yaw), :150-165
-  o[0] = cos(yaw / 2.0); o[1] = 0.0; o[2] = 0.0; o[3] = sin(yaw / 2.0);
-}
-
-template <int T>
-__global__ __launch_bounds__(T) void k_keyframe_reset(StreamArgs a, const unsigned char* __restrict__ mask,
-                                                      double* __restrict__ edge_all) {
-  const int b = blockIdx.x, tid = threadIdx.x;
-  if (b >= a.B) return;
-  if (mask && !mask[b]) return;
-  const int n = a.n, ld = a.ld;
-  double* xg = a.x + a.si(b) * a.nxs;
-  double* P = a.P + a.si(b) * n * ld;
-  const double* q = xg + xATT;
-  const double qw = q[0], qx = q[1], qy = q[2], qz = q[3];
-  const double yaw = q_yaw_dev(q);
-  const double roll = atan2(2.0 * (qw * qx + qy * qz), 1.0 - 2.0 * (qx * qx + qy * qy));    // :211-214
-  const double pitch = asin(2.0 * (qw * qy - qz * qx));                                     // :216-219
-  const double cp = cos(roll), sp = sin(roll), tt = tan(pitch);                             // vi_ekf_kfr.cpp:134-136
-  const double Na[9] = {1.0, sp * tt, cp * tt, 0.0, cp * cp, -cp * sp, 0.0, -cp * sp, sp * sp};   // row-major (:139-142)
-  if (edge_all && tid == 0) {
-    double* e = edge_all + (long)b * 17;
-    for (int i = 0; i < 3; i++) e[i] = xg[xPOS + i];
-    q_from_yaw_dev(yaw, e + 3);
-    for (int j = 0; j < 3; j++)
-      for (int i = 0; i < 3; i++) e[7 + i + 3 * j] = P[(dxPOS + i) + (long)(dxPOS + j) * ld];
-    e[16] = P[(dxATT + 2) + (long)(dxATT + 2) * ld];
-  }
-  __syncthreads();   // (the edge reads P and x before they change)
-  // rows: T = N P
-  for (int j = tid; j < n; j += T) {
-    double* c = P + (long)j * ld;
-    const double a0 = c[dxATT], a1 = c[dxATT + 1], a2 = c[dxATT + 2];
-    c[dxATT] = Na[0] * a0 + Na[1] * a1 + Na[2] * a2;
-    c[dxATT + 1] = Na[3] * a0 + Na[4] * a1 + Na[5] * a2;
-    c[dxATT + 2] = Na[6] * a0 + Na[7] * a1 + Na[8] * a2;
-    c[dxPOS] = 0.0; c[dxPOS + 1] = 0.0; c[dxPOS + 2] = 0.0;
-  }
-  __syncthreads();
-  // columns: P = T N^T
-  for (int i = tid; i < n; i += T) {
-    const double a0 = P[i + (long)dxATT * ld], a1 = P[i + (long)(dxATT + 1) * ld], a2 = P[i + (long)(dxATT + 2) * ld];
-    P[i + (long)dxATT * ld] = a0 * Na[0] + a1 * Na[1] + a2 * Na[2];
-    P[i + (long)(dxATT + 1) * ld] = a0 * Na[3] + a1 * Na[4] + a2 * Na[5];
-    P[i + (long)(dxATT + 2) * ld] = a0 * Na[6] + a1 * Na[7] + a2 * Na[8];
-    P[i + (long)dxPOS * ld] = 0.0; P[i + (long)(dxPOS + 1) * ld] = 0.0; P[i + (long)(dxPOS + 2) * ld] = 0.0;
-  }
-  __syncthreads();
-  // N P N^T of a symmetric P is symmetric; make it so bit for bit (the update kernels rely on it): the attitude rows take
-  // the values of the attitude columns
-  for (int i = tid; i < n; i += T)
-    for (int c = 0; c < 3; c++)
-      if (i < dxATT || i > dxATT + c) P[(dxATT + c) + (long)i * ld] = P[i + (long)(dxATT + c) * ld];
-  if (tid == 0) {
-    const double cr = cos(roll / 2.0), ct = cos(pitch / 2.0), sr = sin(roll / 2.0), st = sin(pitch / 2.0);
-    xg[xPOS] = 0.0; xg[xPOS + 1] = 0.0; xg[xPOS + 2] = 0.0;                                  // :65
-    xg[xATT] = cr * ct; xg[xATT + 1] = sr * ct; xg[xATT + 2] = cr * st; xg[xATT + 3] = -sr * st;   // from_euler(roll,pitch,0)
-  }
-}
-
-// fill every filter with the initial state (vi_ekf.cpp:70-81 / :134-144)
-#ifndef VIEKF_INSTANCES_ONLY
-__global__ void k_reset(StreamArgs a, const double* __restrict__ x0 /*17*/, const double* __restrict__ Pdiag /*n*/) {
-  const int b = blockIdx.x;
-  if (b >= a.B) return;
-  double* xg = a.x + a.si(b) * a.nxs;
-  double* P = a.P + a.si(b) * a.n * a.ld;
-  for (int i = threadIdx.x; i < a.nxs; i += blockDim.x) xg[i] = (i < 17) ? x0[i] : 0.0;
-  const long tot = (long)a.n * a.ld;
-  for (long e = threadIdx.x; e < tot; e += blockDim.x) {
-    const int i = (int)(e % a.ld), j = (int)(e / a.ld);
-    P[e] = (i == j) ? Pdiag[i] : 0.0;
-  }
-  if (threadIdx.x == 0) { a.len[b] = 0; a.flags[b] = 0; }
-}
-#endif
 
 }  // namespace viekf

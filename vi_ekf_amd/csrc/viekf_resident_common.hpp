@@ -4,7 +4,7 @@
 #include <type_traits>
 
 #include "viekf_instance_rows.hpp"
-#include "viekf_kernels_stream.hpp"
+#include "viekf_kernel_args.hpp"
 
 namespace viekf {
 
