@@ -18,3 +18,5 @@ from . import node  # noqa: E402,F401
 from .node import NodeGraph  # noqa: E402,F401
 from . import map  # noqa: E402,F401
 from .map import LandmarkMap  # noqa: E402,F401
+from . import rec  # noqa: E402,F401
+from .rec import FlightRecorder  # noqa: E402,F401

@@ -16,6 +16,7 @@ def sources():
     out.append(os.path.join(os.path.dirname(HERE), "include", "viekf_frame.h"))
     out.append(os.path.join(os.path.dirname(HERE), "include", "viekf_node.h"))
     out.append(os.path.join(os.path.dirname(HERE), "include", "viekf_map.h"))
+    out.append(os.path.join(os.path.dirname(HERE), "include", "viekf_rec.h"))
     return out
 
 

@@ -1,6 +1,6 @@
 // viekf_capi.hip -- the entry points of the C ABI declared in include/viekf.h (libviekf_hip.so), and nothing else: the batch
 // handle is viekf_batch.hpp, kernel choice and launches viekf_dispatch.hpp, argument staging viekf_staging.hpp, the ownership
-// map viekf_resmap.cpp; the batch's companions (diagnostics, frame intake, node graph, landmark map) are viekf_capi_*.hpp,
+// map viekf_resmap.cpp; the batch's companions (diagnostics, frame intake, node graph, landmark map, flight recorder) are viekf_capi_*.hpp,
 // included at the end.  The one HIP translation unit of the host side.  No CPU fallback exists on purpose.
 #include <cmath>
 #include <cstdio>
@@ -1013,3 +1013,4 @@ int viekf_batch_step_n(viekf_batch* b, int32_t K, const double* u, const double*
 #include "viekf_capi_frame.hpp"
 #include "viekf_capi_node.hpp"
 #include "viekf_capi_map.hpp"
+#include "viekf_capi_rec.hpp"
