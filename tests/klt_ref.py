@@ -174,8 +174,9 @@ def _window(pt, n):
     return ip, w4, X, Y
 
 
-def lk(prev_pyr, next_pyr, pts):
-    """-> (next points float32 [n][2], status bool [n])"""
+def lk(prev_pyr, next_pyr, pts, acc=np.float32):
+    """-> (next points float32 [n][2], status bool [n]).  `acc` is the dtype the five window sums accumulate in before they
+    are cast to float32 (float64 states this restatement's own sensitivity to the order of summation)"""
     pts = np.asarray(pts, dtype=np.float32).reshape(-1, 2)
     n = len(pts)
     status = np.ones(n, bool)
@@ -197,9 +198,9 @@ def lk(prev_pyr, next_pyr, pts):
         ival = _bilinear(I, X, Y, w4, True) * F32(32)
         ix = _bilinear(Ix, X, Y, w4, False)
         iy = _bilinear(Iy, X, Y, w4, False)
-        A11 = (ix * ix).reshape(n, -1).sum(1, dtype=np.float32) * FLT_SCALE
-        A12 = (ix * iy).reshape(n, -1).sum(1, dtype=np.float32) * FLT_SCALE
-        A22 = (iy * iy).reshape(n, -1).sum(1, dtype=np.float32) * FLT_SCALE
+        A11 = (ix * ix).reshape(n, -1).sum(1, dtype=acc).astype(np.float32) * FLT_SCALE
+        A12 = (ix * iy).reshape(n, -1).sum(1, dtype=acc).astype(np.float32) * FLT_SCALE
+        A22 = (iy * iy).reshape(n, -1).sum(1, dtype=acc).astype(np.float32) * FLT_SCALE
         D = A11 * A22 - A12 * A12
         with np.errstate(all="ignore"):
             mev = (A22 + A11 - np.sqrt((A11 - A22) * (A11 - A22) + F32(4) * A12 * A12)) / F32(2 * WIN * WIN)
@@ -222,8 +223,8 @@ def lk(prev_pyr, next_pyr, pts):
             run &= ~oob
             jval = _bilinear(J, XJ, YJ, w4j, True) * F32(32)
             diff = jval - ival
-            b1 = (diff * ix).reshape(n, -1).sum(1, dtype=np.float32) * FLT_SCALE
-            b2 = (diff * iy).reshape(n, -1).sum(1, dtype=np.float32) * FLT_SCALE
+            b1 = (diff * ix).reshape(n, -1).sum(1, dtype=acc).astype(np.float32) * FLT_SCALE
+            b2 = (diff * iy).reshape(n, -1).sum(1, dtype=acc).astype(np.float32) * FLT_SCALE
             dx = ((A12 * b2 - A22 * b1) * Dinv).astype(np.float32)
             dy = ((A12 * b1 - A11 * b2) * Dinv).astype(np.float32)
             cur = np.where(run[:, None], cur + np.stack([dx, dy], 1), cur).astype(np.float32)
