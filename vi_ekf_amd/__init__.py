@@ -20,3 +20,5 @@ from . import map  # noqa: E402,F401
 from .map import LandmarkMap  # noqa: E402,F401
 from . import rec  # noqa: E402,F401
 from .rec import FlightRecorder  # noqa: E402,F401
+from . import cam  # noqa: E402,F401
+from .cam import CameraModel  # noqa: E402,F401

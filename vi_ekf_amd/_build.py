@@ -17,6 +17,7 @@ def sources():
     out.append(os.path.join(os.path.dirname(HERE), "include", "viekf_node.h"))
     out.append(os.path.join(os.path.dirname(HERE), "include", "viekf_map.h"))
     out.append(os.path.join(os.path.dirname(HERE), "include", "viekf_rec.h"))
+    out.append(os.path.join(os.path.dirname(HERE), "include", "viekf_cam.h"))
     return out
 
 
