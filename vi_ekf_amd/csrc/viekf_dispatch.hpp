@@ -180,7 +180,7 @@ int unpack_buffer(viekf_batch* b, double* x, double* P) {
   a.smap = nullptr; a.smap_out = nullptr; a.active = nullptr;
   const ResInst& r = kResInst[b->res_inst];
   hipLaunchKernelGGL(res_kernel(b->res_inst, false, b->res_zu), dim3((unsigned)b->B), dim3((r.NW + r.NS) * 64), b->res_lds, b->stream, a,
-                     (RES_FMT_LOAD_PACKED | RES_FMT_P_ONLY) << 1, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, 0L, 0L, nullptr);
+                     launch_pack(false, 1, RES_FMT_LOAD_PACKED | RES_FMT_P_ONLY, 0), nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, 0L, 0L, nullptr);
   HIP_TRY(hipGetLastError());
   return VIEKF_OK;
 }
@@ -217,10 +217,12 @@ int canonicalize_all(viekf_batch* b) {
   return VIEKF_OK;
 }
 
+static_assert(sizeof(BodyCtx) == kBodyCtxBytes, "tests/cpp/fused_lds_model.cpp checks the fused carve-ups with this size");
+
 int setup_tiles(viekf_batch* b) {
   b->tile_inst = -1;
   if (!b->tune_tiles || b->N + 14 > 64 || b->N < 1) return VIEKF_OK;
-  const int NT = 1 + (b->N + 4) / 5;
+  const int NT = tile_nt(b->N);
   int cus = 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->device) != hipSuccess || cus <= 0) cus = 256;
   for (int i = 0; i < kNumTileInst; i++) {
@@ -231,7 +233,7 @@ int setup_tiles(viekf_batch* b) {
     if (b->tune_tiles == 1) continue;
     if (b->tune_tiles == 2 && r.pair) continue;
     if (b->tune_tiles == 3 && !r.pair) continue;
-    const TileLds L(b->N, b->n, b->nxs);
+    const TileLds L(b->N, b->n, b->nxs, sizeof(BodyCtx));
     const size_t lds = sizeof(double) * (size_t)L.total * (r.pair ? 2 : 1);
     if (lds > (size_t)r.max_lds_kb * 1024) continue;
     static size_t have[64][kNumTileInst] = {};
@@ -251,7 +253,7 @@ int setup_resident(viekf_batch* b) {
     if (force && b->tune_res_inst != i) continue;
     if (b->N < r.nmin || b->N > r.nmax) continue;
     if (b->N * (b->N + 1) / 2 > r.RB * r.NW * 64 || b->N > r.NW * 64) continue;
-    const ResLds L(b->N, b->n, b->nxs, res_batched_loads(r.RB, r.NW));
+    const ResLds L(b->N, b->n, b->nxs, res_batched_loads(r.RB, r.NW), sizeof(BodyCtx));
     const size_t lds = sizeof(double) * (size_t)L.total;
     if (lds > (size_t)r.max_lds_kb * 1024) continue;
     if (r.max_lds_kb <= 80 && !force) {   // two small workgroups per CU only pay when the batch fills the CUs more than once
@@ -324,7 +326,7 @@ int launch_resident(viekf_batch* b, bool do_prop, const double* d_u, const doubl
     const int cap = res_mcap(b->N);
     const int mc = (M - m0 < cap) ? (M - m0) : cap;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, b->stream, a,
-                       ((do_prop && m0 == 0) ? (1 | (KP << 16)) : 0) | (fmt << 1) | ((dbg_bits() & 0xff) << 8), d_u, d_dt, d_z ? d_z + 2L * m0 : nullptr,
+                       launch_pack(do_prop && m0 == 0, KP, fmt, dbg_bits()), d_u, d_dt, d_z ? d_z + 2L * m0 : nullptr,
                        d_slot ? d_slot + m0 : nullptr, mc, M, d_R ? d_R + rsm * m0 : nullptr, rsb, rsm,
                        d_res ? d_res + m0 : nullptr);
     HIP_TRY(hipGetLastError());

@@ -2,7 +2,8 @@
 // covariance lives in VGPRs for the complete step (propagate + M sequential feature updates), so
 // P crosses HBM once per step instead of (M+1) times.
 //
-// Files:  viekf_resident_common.hpp   LDS carve-up (ResLds), shared launch state (ResShared), small device helpers
+// Files:  viekf_fused_lds.hpp         LDS carve-up (ResLds), the words of the scratchpad S.sm (res_sm), the launch word
+//         viekf_resident_common.hpp   shared launch state (ResShared), small device helpers
 //         viekf_resident_prop.hpp     the propagate: dynamics hand-over, low-rank coupling set-up (Z records), body strips
 //         viekf_resident_worker.hpp   worker waves: blocks of P in registers -- load, contraction, rank-2 sweeps, extraction, store
 //         viekf_resident_service.hpp  service wave(s): dynamics, state correction, prediction, gate, gain rows
@@ -13,7 +14,7 @@
 // table built by the host (8 x 8 tiles of blocks per 64-lane group: build_resmap, viekf_resmap.cpp).  The 16 body columns
 // P[:,0:16] live in LDS for the whole step (the body rows are their mirror).  A rank-2 sweep needs K for the block's rows and
 // W for its columns; the propagation Phi P Phi^T + Gd Qu Gd^T is a register-tiled K = 24 contraction over one record per
-// row (viekf_resident_common.hpp).  lambda_feat is the same for every feature slot (vi_ekf.cpp:139-144), so the
+// row (viekf_fused_lds.hpp).  lambda_feat is the same for every feature slot (vi_ekf.cpp:139-144), so the
 // partial-update mask Lambda (vi_ekf.cpp:83,146) is ONE 3x3 constant for every feature/feature block.
 #pragma once
 #include "viekf_resident_common.hpp"
@@ -36,7 +37,7 @@ __device__ __forceinline__ void res_prologue(const StreamArgs& a, ResShared& S, 
                                              const double* __restrict__ R_all, long r_stride_b, long r_stride_m,
                                              int* __restrict__ result_all) {
   const int b = blockIdx.x, tid = threadIdx.x;
-  const ResLds L(a.N, a.n, a.nxs, BL);
+  const ResLds L(a.N, a.n, a.nxs, BL, sizeof(BodyCtx));
   S.xs = smem + L.xs; S.Kt = smem + L.Kt; S.Wt = smem + L.Wt; S.Praw = smem + L.Praw; S.lam = smem + L.lam;
   S.sm = smem + L.sm; S.fixadd = smem + L.fixadd; S.fixset = smem + L.fixset; S.Z = smem + L.Z; S.img_len = L.img_len;
   S.phiff = smem + L.phiff; S.Abb = smem + L.Abb; S.Gb = smem + L.Gb; S.Phibb = smem + L.Phibb; S.Mbb = smem + L.Mbb;
@@ -45,7 +46,7 @@ __device__ __forceinline__ void res_prologue(const StreamArgs& a, ResShared& S, 
   S.mslot = reinterpret_cast<int*>(smem + L.mslot);
   S.mseq = reinterpret_cast<int2*>(smem + L.mseq);
   S.ctx = reinterpret_cast<BodyCtx*>(smem + L.ctx);
-  S.N = a.N; S.mcap = res_mcap(a.N); S.n = a.n; S.nf = 3 * a.N; S.len = a.len[b]; S.M = M; S.mstride = m_stride; S.do_prop = do_prop & 1; S.fmt = (do_prop >> 1) & 7; S.dbg = (do_prop >> 8) & 0xff; S.kp = (do_prop >> 16) > 0 ? (do_prop >> 16) : 1; S.B = a.B; S.b = b; S.stamps = a.ws;
+  S.N = a.N; S.mcap = res_mcap(a.N); S.n = a.n; S.nf = 3 * a.N; S.len = a.len[b]; S.M = M; S.mstride = m_stride; S.do_prop = launch_prop(do_prop); S.fmt = launch_fmt(do_prop); S.dbg = launch_dbg(do_prop); S.kp = launch_kp(do_prop); S.B = a.B; S.b = b; S.stamps = a.ws;
   S.si = a.si(b); S.so = a.so(b);
   if (MP && a.kcount) S.kp = a.kcount[b];
   {
@@ -58,8 +59,14 @@ __device__ __forceinline__ void res_prologue(const StreamArgs& a, ResShared& S, 
       S.Lbc[tid] = a.dp->use_partial_update ? (lk + lq - lq * lk) : 1.0;
     }
     // launch constants of the propagate's barrier intervals (res_prop_setup, res_prop_body): read from LDS there, not from memory
-    if (BL && tid >= T - 22) { const int i = tid - (T - 22); S.sm[RES_SM_SQRTQU + i] = (i < 6) ? a.dp->sqrtQu[i] : a.Qx[i - 6]; }
-    if (tid == 0) { S.sm[42] = (do_prop & 1) ? dt_all[b] : 0.0; S.sm[40] = 0.0; S.sm[41] = 0.0; S.sm[44] = 0.0; S.sm[45] = 0.0; S.sm[46] = 0.0; S.sm[49] = 0.0; S.sm[50] = 0.0; S.sm[51] = 0.0; S.sm[32] = 0.0; S.sm[33] = 0.0; S.sm[52] = 0.0; S.sm[53] = 0.0; S.sm[54] = 0.0; S.sm[36] = 0.0; S.sm[37] = 0.0; }
+    if (BL && tid >= T - 22) { const int i = tid - (T - 22); S.sm[res_sm::SQRTQU + i] = (i < 6) ? a.dp->sqrtQu[i] : a.Qx[i - 6]; }
+    if (tid == 0) {   // dt, and the words that must read zero when the step starts (res_sm)
+      constexpr unsigned long long zero = sm_zero_mask(res_sm::kWords);
+      S.sm[res_sm::DT] = launch_prop(do_prop) ? dt_all[b] : 0.0;
+#pragma unroll
+      for (int w = 0; w < res_sm::CTRL_WORDS; w++)
+        if ((zero >> w) & 1) S.sm[w] = 0.0;
+    }
     for (int mm_ = tid; mm_ < M; mm_ += T) {
       const int slot = slot_all[(long)b * m_stride + mm_];
       const double z0 = z_all[((long)b * m_stride + mm_) * 2], z1 = z_all[((long)b * m_stride + mm_) * 2 + 1];
@@ -106,7 +113,7 @@ __global__ __launch_bounds__((NW + NS) * 64, (NW <= 3) ? 2 : 1) void k_step_resi
 #ifdef VIEKF_ABLATE
   {   // timing experiment (DESIGN.md 5.2, r04 xxxi): are the two workgroups of a CU better off OUT of step?  Half of the workgroups
       // start late by ((bits >> 4) & 7) x 8 us; bit 7 picks which half: 0 = the odd ones, 1 = every second block of 256
-    const int bits = (do_prop >> 8) & 0xff, st = (bits >> 4) & 7;
+    const int bits = launch_dbg(do_prop), st = (bits >> 4) & 7;
     const bool late = (bits & 128) ? ((blockIdx.x >> 8) & 1) != 0 : (blockIdx.x & 1) != 0;
     if (st && late) {
       const unsigned long long t0 = __builtin_amdgcn_s_memtime();

@@ -1,7 +1,8 @@
 // viekf_kernels_tiles.hpp -- "tile" kernel family (r03): the fused step (propagate(s) + M sequential feature updates, P on chip for
 // the whole step) with P held as 16 x 16 tiles in the fp64 matrix cores' accumulator layout.
 //
-// Files:  viekf_tiles_common.hpp   why, the row space, LDS carve-up (TileLds), prologue
+// Files:  viekf_fused_lds.hpp      LDS carve-up (TileLds), the words of the scratchpad S.sm (tile_sm), the launch word
+//         viekf_tiles_common.hpp   why, the row space, prologue
 //         viekf_tiles_worker.hpp   worker waves: load, tile propagate, rank-4 MFMA sweeps, column extraction, store
 //         viekf_tiles_service.hpp  service wave: dynamics, state correction, prediction, gate
 //         viekf_resident_prop.hpp  (shared with the resident family) the propagate's set-up and body strips
@@ -44,8 +45,8 @@ __global__ __launch_bounds__((NW + 1) * 64, (NW <= 3) ? 2 : 1) void k_step_tiles
 template <int MP>
 __device__ __forceinline__ void tile_absent(const TileShared& S, int do_prop, int trips) {
   __syncthreads();  // B0
-  if (do_prop & 1) {
-    const int nkp = MP ? ((do_prop >> 16) > 0 ? (do_prop >> 16) : 1) : 1;
+  if (launch_prop(do_prop)) {
+    const int nkp = MP ? launch_kp(do_prop) : 1;
     for (int kp = 0; kp < nkp; kp++)
       for (int i = 0; i < 5; i++) __syncthreads();   // B1p B2p B2q B3p B4p
     __syncthreads();  // B4q
@@ -71,13 +72,13 @@ __global__ __launch_bounds__(512, 1) void k_step_tiles_pair(StreamArgs a, int do
   const bool on0 = b0 < a.B && (!a.active || a.active[b0]), on1 = b1 < a.B && (!a.active || a.active[b1]);
   if (!on0 && !on1) return;                                // (the whole workgroup: before any barrier)
   const bool present = half ? on1 : on0;
-  const TileLds L(a.N, a.n, a.nxs);
+  const TileLds L(a.N, a.n, a.nxs, sizeof(BodyCtx));
   double* mine = smem + (size_t)half * L.total;
   TileShared S;
   const int tl = tid & 255;                                // thread index inside the filter's half
   tile_prologue<256>(a, S, mine, present ? b : 0, tl, present, do_prop, dt_all, z_all, slot_all, M, m_stride, R_all, r_stride_b, r_stride_m,
                      result_all);
-  const int trips = max((int)smem[L.sm + 60], (int)smem[L.total + L.sm + 60]);
+  const int trips = max((int)smem[L.pair_word(0, tile_sm::TRIPS)], (int)smem[L.pair_word(1, tile_sm::TRIPS)]);
   if (!present) { tile_absent<MP>(S, do_prop, trips); return; }
   // half 0: waves 0, 1, 2 work, wave 3 serves;  half 1: wave 4 serves, waves 5, 6, 7 work
   const int wl = wave & 3;

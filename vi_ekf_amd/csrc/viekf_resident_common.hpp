@@ -1,78 +1,18 @@
-// viekf_resident_common.hpp -- resident (fused-step) kernel family: LDS carve-up, shared launch state and the small device
-// helpers both roles use.  Overview of the family: viekf_kernels_resident.hpp.
+// viekf_resident_common.hpp -- resident (fused-step) kernel family: shared launch state and the small device helpers both roles
+// use.  The LDS carve-up (ResLds), the words of the scratchpad S.sm (res_sm) and the launch word: viekf_fused_lds.hpp.  Overview of
+// the family: viekf_kernels_resident.hpp.
 #pragma once
 #include <type_traits>
 
+#include "viekf_fused_lds.hpp"
 #include "viekf_instance_rows.hpp"
 #include "viekf_kernel_args.hpp"
 
 namespace viekf {
 
-// Format bits of a fused launch (bits 1..3 of the launch word, uniform over the launch, set by launch_resident): which form of
-// P the launch loads and which it stores -- canonical column-major P[n][ld] (lower triangle valid) or the packed image of the
-// kernel's own registers and LDS (ResPack, viekf_instance_rows.hpp) -- and the conversion-only launch (no propagate, M = 0):
-// it leaves x, the status words and the result buffers alone, so packed -> canonical is an identity on everything but the form.
-constexpr int RES_FMT_LOAD_PACKED = 1, RES_FMT_STORE_PACKED = 2, RES_FMT_P_ONLY = 4;
-
 #ifndef RES_INLINE
 #define RES_INLINE __forceinline__
 #endif
-// Propagate in low-rank coupling form.  A_fb[I] = Afv_I E_v + Afg_I E_g and the bias rows of A_bb are zero
-// (vi_ekf_dyn.cpp:55-71,121-128), so  Phi_fb[I] = D_I Psi  with a per-feature 3x9  D_I = [M1 | M3 | M2],
-//   M1 = (Afv + dt/2 Aff Afv) dt,  M3 = Afv dt^2/2,  M2 = (Afg + dt/2 Aff Afg) dt,   Psi = [E_v ; A_bb[vel rows] ; E_g]  (9 x 16),
-// and with  Pi = Psi P_bb Psi^T,  V_I = Phi_ff[I] P[I, body],  Ut_I = D_I Pi / 2 + V_I Psi^T  (3x9):
-//   P+[I,J] = Phi_ff[I] P[I,J] Phi_ff[J]^T + Ut_I D_J^T + D_I Ut_J^T + Gs_I Gs_J^T (+ Qx),   Gs = Gd sqrt(Qu)
-//   P+[I,body] = V_I Phi_bb^T + D_I Xi + Gs_I Gs_b^T,   Xi = Psi (P_bb Phi_bb^T)
-// -- a K = 24 contraction over ONE record per row (the symmetric form needs no separate X / Y operands):
-//   Z[row] = { (Ut[k], D[k]) k = 0..8 interleaved | Gs[0..5] | pad }      ZS doubles per row
-constexpr int ZK = 9;    // rank of the feature/body coupling
-constexpr int ZS = 26;   // row stride of Z: 6 ZS = 28 (mod 64 dwords), consecutive features land on distinct 16-byte bank groups
-
-// measurements per launch (the host chunks longer lists: P then makes one more HBM round trip per chunk): a frame that measures
-// every feature once fits one launch.  (64 up to 64 features: the headline instance, <7, 3> at N = 50, takes 81 488 of its
-// 81 920 bytes of LDS -- 432 are left.)
-__host__ __device__ inline int res_mcap(int N) { return N > 64 ? 80 : 64; }
-
-constexpr int RES_SM_SQRTQU = 64, RES_SM_QXB = 70;   // see ResLds::sm (resident family only: the tile family's sm has 64 words)
-
-struct ResLds {  // LDS carve-up in doubles, shared by host (size) and device (offsets)
-  int xs, Kt, Wt, Praw, lam, sm, fixadd, fixset, Z, phiff, Abb, Gb, Phibb, Mbb, Gdb, Pbb, T16, xdb, ctx, Pbc, PhibbT, Pd, PsiP, Pi, Xi, AvG, Lbc, mslot, mseq, mz, mR, img_len, total;
-  __host__ __device__ ResLds(int N, int n, int nxs, bool staged) {   // staged: res_batched_loads of the instance
-    const int nf = 3 * N;
-    int o = 0;
-    auto take = [&](int cnt) { int r = o; o += (cnt + 1) & ~1; return r; };
-    xs = take(nxs);
-    lam = take(n);
-    sm = take(staged ? 64 + 22 : 64);   // [0..15],[16..31] two measurement mailboxes {Hb(4) res(2) Sinv(4) verdict}, [40..41] fix mailboxes
-                     // non-empty, [42] dt, [44..46] NaN-guard words (phase mod 3), [49] count of worker waves that have
-                     // published the next raw columns (int), [50..51] gate verdicts (phase parity), [64..69] sqrt(Qu) and
-                     // [70..85] Qx of the body rows: launch constants the propagate reads inside its barrier intervals
-                     // (RES_SM_SQRTQU, RES_SM_QXB: at fixed offsets from sm, they cost no pointer of their own; only where staged)
-    fixadd = take(2 * (N > 0 ? N : 1)); fixset = take(2 * (N > 0 ? N : 1));
-    // Z, Phi_ff and the two-lives region are contiguous: at store time all of it is dead and holds the P image
-    Z = take(nf * ZS > 4 * n ? nf * ZS : 4 * n);   // propagate: the records; updates: second gain-row buffer; store: P image
-    phiff = take(9 * (N > 0 ? N : 1));
-    // one region, two lives: the propagate's body-sized scratch | the update loop's gain rows, raw columns and zeta blocks
-    const int u0 = o;
-    Abb = take(256); Gb = take(96); Phibb = take(256); PhibbT = take(256); Gdb = take(96); T16 = take(256);
-    PsiP = take(ZK * 16); Pi = take(ZK * ZK); Xi = take(ZK * 16); AvG = take(18);
-    const int uprop = o;
-    o = u0;
-    Kt = take(2 * n); Wt = take(2 * n);
-    Praw = take(4 * n > 256 ? 4 * n : 256);   // two buffers [n][2]: raw column pairs of the next two measurements
-    Pd = take(4 * (N > 0 ? N : 1));           // zeta-zeta 2x2 diagonal blocks, handed from the workers to the service lanes
-    if (uprop > o) o = uprop;
-    img_len = o - Z;
-    Mbb = take(256); Pbb = take(256);
-    xdb = take(16);
-    ctx = take((int)((sizeof(BodyCtx) + 7) / 8));
-    Pbc = take(nf * 16);
-    Lbc = take(48);   // Lambda of (feature row q, body column k): [3][16]
-    const int mc = res_mcap(N);   // measurements per launch
-    mslot = take(mc / 2); mseq = take(mc); mz = take(2 * mc); mR = take(4 * mc);
-    total = o;
-  }
-};
 // ------------------------------------------------------------------------------------------------
 // fused step: [propagate] + M feature updates with P resident in registers, WARP-SPECIALISED:
 //   worker waves (NW x 64 threads) own P and run only the lean contraction / sweep code;
@@ -178,11 +118,7 @@ __device__ __forceinline__ void res_words(const int* __restrict__ resmap, int t,
 #pragma unroll
   for (int ia = 0; ia < RB; ia++) w[ia] = resmap[ia * TW + t];
 }
-// Which instances do so, and stage sqrt(Qu) / Qx in LDS: all but the one-workgroup-per-CU instances <1,7>, <2,7>, <3,7> -- 1 to 3
-// blocks per thread leave next to nothing to batch, and their unit-Lambda step measured 0.7 - 1.4 % SLOWER with the batches -- and
-// <8,6> at the register file's end (its propagate-only launch +1.8 %, more spilled dwords).  Those compile to the instruction
-// stream they had before (profiles/serial_loads/).
-constexpr bool res_batched_loads(int RB, int NW) { return NW != 7 && RB != 8; }
+// (which instances do so, and stage sqrt(Qu) / Qx in LDS: res_batched_loads, viekf_fused_lds.hpp)
 // Which instances spread the block loads of P over the propagate's set-up and first wait for them behind B3p (res_worker, switch
 // SU): the single-propagate kernels of <4,3>, <6,3>, <7,3> and <5,6> -- the instances that timed faster or equal with it, each
 // against the parent (profiles/setup_under_load/instances_ab.md).  <2,1>, <2,2>, <3,2> (two or three blocks per thread: little to

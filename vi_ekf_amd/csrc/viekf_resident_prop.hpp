@@ -117,7 +117,7 @@ __device__ RES_INLINE void res_fix_depth(double* xf, const DevParams* p, double*
 //   [B2p..B2q]  Gs_b = M_bb G_b dt sqrt(Qu), T16 = Phi_bb P_bb, Pi = Psi P_bb Psi^T
 //   [B2q..B3p]  Ut = D Pi / 2 + V Psi^T  (the even Z slots), Xi = Psi T16^T
 // Barriers B1p, B2p, B2q inside; the caller continues with B3p.
-// LDSC: sqrt(Qu) from the resident family's LDS copy (ResLds::sm, RES_SM_SQRTQU) -- read from memory, the constant's round
+// LDSC: sqrt(Qu) from the resident family's LDS copy (res_sm::SQRTQU, viekf_fused_lds.hpp) -- read from memory, the constant's round
 // trip sits inside an interval the whole workgroup waits on, once per interval.  (The tile family's sm has no such words.)
 // hook(k), k = 0 .. 2 as std::integral_constant: called behind B1p, B2p and B2q (the worker's spread block loads)
 struct ResNoHook { template <class K> __device__ __forceinline__ void operator()(K) const {} };
@@ -129,11 +129,11 @@ __device__ __forceinline__ void res_prop_setup(const StreamArgs& a, const ResSha
   double* Z = S.Z; double* phiff = S.phiff;
   double* Phibb = S.Phibb; double* Mbb = S.Mbb; double* Gdb = S.Gdb; double* T16 = S.T16;
   __syncthreads();  // B1p : body Jacobian, raw feature blocks and Phi_ff ready (service), and this propagate's dt
-  const double dt = S.sm[42];
+  const double dt = S.sm[res_sm::DT];   // (the same word in both families: tile_sm::DT)
   hook(std::integral_constant<int, 0>{});
 
   // ---- [B1p..B2p]
-  for (int e = tid; e < nf; e += TW) res_feature_expand_row(e / 3, e % 3, dt, Z, S.Gb, S.AvG, LDSC ? S.sm + RES_SM_SQRTQU : prm.sqrtQu);
+  for (int e = tid; e < nf; e += TW) res_feature_expand_row(e / 3, e % 3, dt, Z, S.Gb, S.AvG, LDSC ? S.sm + res_sm::SQRTQU : prm.sqrtQu);
   for (int e = TW - 1 - tid; e < 256; e += TW) {   // body transition blocks (vi_ekf.cpp:302-303), from the last threads
     const int r = e >> 4, c = e & 15;
     double a2 = 0.0;
@@ -182,7 +182,7 @@ __device__ __forceinline__ void res_prop_setup(const StreamArgs& a, const ResSha
     double sv = 0.0;
 #pragma unroll 4
     for (int c = 0; c < 16; c++) sv += Mbb[r * 16 + c] * S.Gb[c * 6 + k];
-    Gdb[e] = sv * dt * (LDSC ? S.sm[RES_SM_SQRTQU + k] : prm.sqrtQu[k]);
+    Gdb[e] = sv * dt * (LDSC ? S.sm[res_sm::SQRTQU + k] : prm.sqrtQu[k]);
   }
   for (int e = tid; e < ZK * ZK; e += TW) {   // Pi = (Psi P_bb) Psi^T
     const int q = e / ZK, j = e - q * ZK;
@@ -253,7 +253,7 @@ __device__ __forceinline__ void res_prop_setup(const StreamArgs& a, const ResSha
 // P+[feature rows, body columns] = V Phi_bb^T + D Xi + Gs Gs_b^T, in LDS and in place (a tile's rows are read before they are
 // written, by the same wave), and the body block (-> Mbb).  (nf x 16)(16 x 16) + (nf x 16)(16 x 16) on the matrix cores, one
 // 16-row tile per wave and turn, 4 + 4 k-steps: the second product's k runs over D[0..8], Gs[0..5] and one zero.
-// LDSC: Qx of the 16 body rows from the resident family's LDS copy (RES_SM_QXB: see res_prop_setup), else a.Qx.
+// LDSC: Qx of the 16 body rows from the resident family's LDS copy (res_sm::QXB: see res_prop_setup), else a.Qx.
 template <int TW, bool LDSC = false>
 __device__ __forceinline__ void res_prop_body(const StreamArgs& a, const ResShared& S, int tid) {
   const int nf = S.nf;
@@ -317,7 +317,7 @@ __device__ __forceinline__ void res_prop_body(const StreamArgs& a, const ResShar
 #pragma unroll
     for (int r4 = 0; r4 < 4; r4++) {
       const int r = lk + 4 * r4, c = lr;                           // a result lane holds column lr of rows lk + 4 r4
-      S.Mbb[r * 16 + c] = acc[r4] + ((r == c) ? (LDSC ? S.sm[RES_SM_QXB + r] : a.Qx[r]) : 0.0); // P_bb+ staged in Mbb (T16 / Pbb are still being read)
+      S.Mbb[r * 16 + c] = acc[r4] + ((r == c) ? (LDSC ? S.sm[res_sm::QXB + r] : a.Qx[r]) : 0.0); // P_bb+ staged in Mbb (T16 / Pbb are still being read)
     }
   }
 }

@@ -28,7 +28,7 @@ __device__ __forceinline__ void res_service(const StreamArgs& a, const ResShared
   RES_STAMP(S, lane == 0, 0);
   // The dynamics of the propagate need only the state (in LDS since the prologue): they run BEFORE B0, while the worker
   // waves are still loading P from HBM, instead of holding every worker up afterwards.
-  double dt = sm[42];
+  double dt = sm[res_sm::DT];
   // dynamics of propagate kp (of S.kp): body Jacobian on lane 0 (+ A_v G_b for the workers' expansion of the feature rows),
   // then one feature per lane
   auto dyn_body = [&](int kp) {
@@ -71,9 +71,9 @@ __device__ __forceinline__ void res_service(const StreamArgs& a, const ResShared
 #pragma unroll
       for (int i = 0; i < 17; i++) xs[i] = xo[i];
     }
-    if (PRIMARY && lane == 0) sm[40 + par] = 0.0;
+    if (PRIMARY && lane == 0) sm[res_sm::fix_word(ROLE, par)] = 0.0;
     for (int f = lane; PRIMARY && f < len; f += 64)   // fix_depth (vi_ekf.cpp:311): state here, covariance through the mailbox
-      res_fix_depth(xs + xZ + 5 * f, a.dp, &S.fixadd[par * N + f], &S.fixset[par * N + f], &sm[40 + par], &flag);
+      res_fix_depth(xs + xZ + 5 * f, a.dp, &S.fixadd[par * N + f], &S.fixset[par * N + f], &sm[res_sm::fix_word(ROLE, par)], &flag);
     par ^= 1;
     RES_STAMP(S, lane == 0, 6);
     __syncthreads();  // B3p
@@ -94,7 +94,7 @@ __device__ __forceinline__ void res_service(const StreamArgs& a, const ResShared
     RES_STAMP(S, lane == 0, 8);
     if (PRIMARY && MP && kp + 1 < nkp) {
       dt = dt_next;
-      if (lane == 0) sm[42] = dt;
+      if (lane == 0) sm[res_sm::DT] = dt;
       dyn_feat(dt);
     }
    }
@@ -169,14 +169,14 @@ __device__ __forceinline__ void res_service(const StreamArgs& a, const ResShared
   // Gain rows of a measurement for ALL n rows (three per lane) from its raw column pair pr (this lane's rows):
   //   W_i = P[i, j0:j0+2] Hb^T,  K_i = W_i S^-1   (vi_ekf_meas.cpp:241).
   // Also leaves the NaN guard (:247; a NaN in H makes every K row NaN, so testing K covers the H test) and the gate verdict
-  // for the workers' next phase.
+  // for the workers' phase `phase`, in that phase's words.
   const double lraw[3] = {S.lam[rid0], S.lam[rid1], S.lam[rid2]};
   // The rows are dealt by ROLE (a feature lane its three rows, the attitude lane rows 6..8, a linear body lane its one row),
   // so a lane's own rows of K and W -- all that its state correction needs in the next phase -- stay in registers.
   struct Rows { double2 kA, wA, kB, wB, kC, oA, oB, oC; int bad; };   // (oX: the row's operand of next_rows -- K for a feature row, W for a body row)
   const bool three = isfeat || isatt;   // lanes with three distinct rows (the others would write the same row three times)
   const int ridv[3] = {rid0, rid1, rid2};
-  auto gain_rows = [&](const Meas& q, int nanword, int gateword, const double2 (&pr)[3], double* Kd, Rows& o) {
+  auto gain_rows = [&](const Meas& q, int phase, const double2 (&pr)[3], double* Kd, Rows& o) {
     double* Wd = Kd + 2 * n;                             // (Kd: destination buffer)
     int bad = 0;
     double2 wv[3], kv[3];
@@ -192,9 +192,9 @@ __device__ __forceinline__ void res_service(const StreamArgs& a, const ResShared
       if (rowlane && (k0 != k0 || k1 != k1)) bad = 1;
     }
     bad = __any(bad);
-    if (lane == 0) {   // (two service waves: each its own NaN word, 8 apart; the gate verdict is the feature wave's to publish)
-      sm[nanword + (ROLE == 2 ? 8 : 0)] = bad ? 1.0 : 0.0;
-      if (PRIMARY) sm[gateword] = q.gate;
+    if (lane == 0) {   // (two service waves: each its own NaN word; the gate verdict is the feature wave's to publish)
+      sm[res_sm::nan_word(ROLE, phase)] = bad ? 1.0 : 0.0;
+      if (PRIMARY) sm[res_sm::gate_word(phase)] = q.gate;
     }
     o.kA = kv[0]; o.wA = wv[0]; o.kB = kv[1]; o.wB = wv[1]; o.kC = kv[2]; o.bad = bad;
     o.oA = isfeat ? kv[0] : wv[0]; o.oB = isfeat ? kv[1] : wv[1]; o.oC = isfeat ? kv[2] : wv[2];
@@ -245,29 +245,31 @@ __device__ __forceinline__ void res_service(const StreamArgs& a, const ResShared
     else { o[1] = o[0]; o[2] = o[0]; }
     if (isfeat && fid == slot) o[1].x = o[0].y;   // the measured feature's own zeta block: lower = upper, as the workers keep it
   };
-  // two service waves: the measurement's uniform values cross from the feature wave to the body wave through sm[16 mb ..],
-  // published by a sequence number in sm[32 + mb] (an int; each mailbox sees increasing numbers)
+  // two service waves: the measurement's uniform values cross from the feature wave to the body wave through mailbox mb of the
+  // scratchpad (res_sm::mbox), published by its sequence number (res_sm::mbox_seq: an int; each mailbox sees increasing numbers)
   auto send = [&](const Meas& q, int mb, int seq) {
     if (lane == 0) {
-      double* d = sm + 16 * mb;
-      d[0] = q.h0; d[1] = q.h1; d[2] = q.h2; d[3] = q.h3; d[4] = q.r0; d[5] = q.r1;
-      d[6] = q.s0; d[7] = q.s1; d[8] = q.s2; d[9] = q.s3; d[10] = q.gate;
+      using namespace res_sm;
+      double* d = sm + mbox(mb);
+      d[MB_H0] = q.h0; d[MB_H1] = q.h1; d[MB_H2] = q.h2; d[MB_H3] = q.h3; d[MB_R0] = q.r0; d[MB_R1] = q.r1;
+      d[MB_S0] = q.s0; d[MB_S1] = q.s1; d[MB_S2] = q.s2; d[MB_S3] = q.s3; d[MB_GATE] = q.gate;
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
 #ifdef VIEKF_TEST_STALL   // test build only (tests/test_gpu_stall.py): filter 0 never publishes its third hand-over -- the body
     if (S.b == 0 && seq == 3) return;   // wave's bounded wait must give up, raise VIEKF_FLAG_INTERNAL and the launch must end
 #endif
-    if (lane == 0) *(lds_vint_t*)(sm + 32 + mb) = seq;
+    if (lane == 0) *(lds_vint_t*)(sm + res_sm::mbox_seq(mb)) = seq;
   };
   auto recv = [&](Meas& q, int mb, int seq) {
-    lds_vint_t* w = (lds_vint_t*)(sm + 32 + mb);
+    lds_vint_t* w = (lds_vint_t*)(sm + res_sm::mbox_seq(mb));
     int spins = 0;
     while (*w != seq && spins < (1 << 22)) { __builtin_amdgcn_s_sleep(1); spins++; }
     if (spins >= (1 << 22)) flag |= FLAG_INTERNAL;   // (a bounded wait that gives up must say so)
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    const double* d = sm + 16 * mb;
-    q.h0 = d[0]; q.h1 = d[1]; q.h2 = d[2]; q.h3 = d[3]; q.r0 = d[4]; q.r1 = d[5];
-    q.s0 = d[6]; q.s1 = d[7]; q.s2 = d[8]; q.s3 = d[9]; q.gate = d[10];
+    using namespace res_sm;
+    const double* d = sm + mbox(mb);
+    q.h0 = d[MB_H0]; q.h1 = d[MB_H1]; q.h2 = d[MB_H2]; q.h3 = d[MB_H3]; q.r0 = d[MB_R0]; q.r1 = d[MB_R1];
+    q.s0 = d[MB_S0]; q.s1 = d[MB_S1]; q.s2 = d[MB_S2]; q.s3 = d[MB_S3]; q.gate = d[MB_GATE];
   };
   Meas cur = {}, nxt = {};
   Rows crow = {}, nrow = {};
@@ -280,7 +282,7 @@ __device__ __forceinline__ void res_service(const StreamArgs& a, const ResShared
     double2 pr0[3];
 #pragma unroll
     for (int u = 0; u < 3; u++) pr0[u] = lds_ld2(S.Praw + 2 * ridv[u]);   // (the first raw columns: buffer 0, published before Bp)
-    gain_rows(cur, 44, 50, pr0, S.Kt, crow);
+    gain_rows(cur, 0, pr0, S.Kt, crow);
   }
   int2 sq = S.mseq[min(m, S.mcap - 1)];
   __syncthreads();  // B1
@@ -296,7 +298,7 @@ __device__ __forceinline__ void res_service(const StreamArgs& a, const ResShared
     sq = S.mseq[min(mnext, S.mcap - 1)];   // next iteration's table entry (static data): its latency hides behind this update
     const bool gated = cur.gate != 0.0;
     // NaN guard (vi_ekf_meas.cpp:247), decided over every row of K in gain_rows (two service waves: the other one's rows too)
-    const bool bad = crow.bad != 0 || (ROLE != 0 && sm[44 + cnt % 3 + (ROLE == 2 ? 0 : 8)] != 0.0);
+    const bool bad = crow.bad != 0 || (ROLE != 0 && sm[res_sm::nan_word(ROLE == 2 ? 1 : 2, cnt)] != 0.0);
     const double r0 = cur.r0, r1 = cur.r1;
     double2 prn[3] = {};
     if constexpr (MERGE) {
@@ -376,16 +378,16 @@ __device__ __forceinline__ void res_service(const StreamArgs& a, const ResShared
     }
     RES_STAMP(S, lane == 0 && it_ < 8, 128 + 4 * it_ + 1);
     RES_MARK("service.fix_depth");
-    // (fix_depth mailbox flag: one word per service wave -- [40 + par] / [36 + par] -- each wave clears and sets its own)
-    constexpr int FIXW = (ROLE == 2) ? 36 : 40;
-    if (lane == 0) sm[FIXW + par] = 0.0;
+    // (fix_depth mailbox flag: one word per service wave, each wave clears and sets its own)
+    const int fixw = res_sm::fix_word(ROLE, par);
+    if (lane == 0) sm[fixw] = 0.0;
     // fix_depth (vi_ekf_meas.cpp:271; a gated update returns before it, :238): almost never fires -- one wave-wide test
     const bool odd_depth = !gated && isfeat && fid < len && !(lin >= 0.0 && lin <= 1e2);
     if (__any(odd_depth)) {
       if (odd_depth) {
         VIEKF_COLD_BEGIN();
-        fix_depth_rule(lin, rho_reset, flag, [&](double e2) { S.fixadd[par * N + fid] = e2; sm[FIXW + par] = 1.0; },
-                       [&] { S.fixset[par * N + fid] = 1.0; sm[FIXW + par] = 1.0; });
+        fix_depth_rule(lin, rho_reset, flag, [&](double e2) { S.fixadd[par * N + fid] = e2; sm[fixw] = 1.0; },
+                       [&] { S.fixset[par * N + fid] = 1.0; sm[fixw] = 1.0; });
         VIEKF_COLD_END();
       }
     }
@@ -399,7 +401,7 @@ __device__ __forceinline__ void res_service(const StreamArgs& a, const ResShared
     if (PRIMARY && result_all && lane == 0) result_all[(long)S.b * S.mstride + m] = gated ? 1 : 0;
     RES_STAMP(S, lane == 0 && it_ < 8, 128 + 4 * it_ + 3);
     RES_MARK("service.gain_rows");
-    if (slot_next >= 0) gain_rows(nxt, 44 + (cnt + 1) % 3, 50 + ((cnt + 1) & 1), prn, (cnt & 1) ? S.Kt : S.Z, nrow);
+    if (slot_next >= 0) gain_rows(nxt, cnt + 1, prn, (cnt & 1) ? S.Kt : S.Z, nrow);
     RES_MARK("service.phase_tail");
     cur = nxt;
     crow = nrow;

@@ -124,7 +124,7 @@ __device__ __forceinline__ void res_body_items(const ResShared& S, const double*
 }
 // (The service wave takes no share of the body-column items: with the tile map its chain is the longest wave of an update and
 //  every share > 0 measured slower -- N = 50, B = 1024: 0 / N / 2 N items -> 0.348 / 0.347 / 0.353 ms per step.)
-// BL: the instance issues its launch-constant loads in batches (res_batched_loads, viekf_resident_common.hpp)
+// BL: the instance issues its launch-constant loads in batches (res_batched_loads, viekf_fused_lds.hpp)
 // SU: the block loads of P are in flight across B0 and the propagate's set-up (res_setup_under_load, same file), and their issue is
 //     spread over the set-up's barrier intervals: chunk k of 4 = blocks [RB k / 4, RB (k + 1) / 4), chunk 0 ahead of B0, chunks 1 .. 3
 //     behind B1p, B2p and B2q (the hook of res_prop_setup) -- with all of them issued at once a wave stands at the issue while the
@@ -292,7 +292,7 @@ __device__ __forceinline__ void res_worker(const StreamArgs& a, const ResShared&
   const bool partial = SU ? partial_su : prm.use_partial_update != 0;
   int par = 0;  // fix_depth mailbox parity (mirrors the service wave)
   constexpr int NSV = (T - TW) / 64;   // service waves: with one, the second wave's flag words are not read at all
-  auto fix_word = [&](int mb) -> double { return (NSV > 1) ? S.sm[40 + mb] + S.sm[36 + mb] : S.sm[40 + mb]; };
+  auto fix_word = [&](int mb) -> double { return (NSV > 1) ? S.sm[res_sm::fix_word(1, mb)] + S.sm[res_sm::fix_word(2, mb)] : S.sm[res_sm::fix_word(0, mb)]; };
   RES_STAMP(S, tid == 0, 64);
   __syncthreads();  // B0
   RES_STAMP(S, tid == 0, 65);
@@ -581,8 +581,8 @@ __device__ __forceinline__ void res_worker(const StreamArgs& a, const ResShared&
     const double* wP = kP + 2 * n;
     __builtin_amdgcn_s_setprio(1);
     const double fixpending = fix_word(par ^ 1);   // posted before the barrier by the service wave
-    const double gflag = S.sm[50 + (cnt & 1)];          // gate verdict of this measurement (service, previous phase)
-    const double nanw = (NSV > 1) ? S.sm[44 + cnt % 3] + S.sm[52 + cnt % 3] : S.sm[44 + cnt % 3];   // (the second word: a second service wave's rows)
+    const double gflag = S.sm[res_sm::gate_word(cnt)];   // gate verdict of this measurement (service, previous phase)
+    const double nanw = (NSV > 1) ? S.sm[res_sm::nan_word(1, cnt)] + S.sm[res_sm::nan_word(2, cnt)] : S.sm[res_sm::nan_word(0, cnt)];   // (the second word: a second service wave's rows)
     sq = S.mseq[min(mnext, S.mcap - 1)];                 // next iteration's table entry (static data)
     RES_STAMP(S, tid == 0 && it_ < 8, 80 + 4 * it_ + 1);
     RES_STAMP(S, (tid & 63) == 0 && it_ == 3, 192 + 4 * (tid >> 6) + 0);

@@ -18,47 +18,12 @@
 // Register content of a tile (TI, TJ), lane l, register r (the instruction's C/D layout: row = (l >> 4) + 4 r, col = l & 15):
 //     X[r] = P[ prow(TI, l & 15) ][ prow(TJ, (l >> 4) + 4 r) ]
 // i.e. the lane index runs along the ROWS of P (column-major in HBM: 128-byte runs per 16 lanes for loads and stores).
+// LDS carve-up (TileLds) and the words of the scratchpad S.sm (tile_sm): viekf_fused_lds.hpp.
 #pragma once
 #include "viekf_resident_common.hpp"
 #include "viekf_resident_prop.hpp"
 
 namespace viekf {
-
-__host__ __device__ inline int tile_nt(int N) { return 1 + (N + 4) / 5; }
-
-struct TileLds {  // LDS carve-up in doubles, shared by host (size) and device (offsets)
-  int xs, lam, sm, fixadd, fixset, Z, phiff, Abb, Gb, Phibb, PhibbT, Gdb, T16, PsiP, Pi, Xi, AvG, Cb, Eb, Pd, Mbb, Pbb, xdb, ctx, Pbc,
-      mslot, mseq, mz, mR, total;
-  __host__ __device__ TileLds(int N, int n, int nxs) {
-    const int nf = 3 * N, NQ = 16 * tile_nt(N);
-    int o = 0;
-    auto take = [&](int cnt) { int r = o; o += (cnt + 1) & ~1; return r; };
-    xs = take(nxs);
-    lam = take(n);
-    sm = take(64);          // [0..15] two measurement mailboxes {g00, g01, g11, skip}; [40..41] fix mailboxes non-empty; [42] dt;
-                            // [44..46] NaN-in-column words (phase mod 3)
-    fixadd = take(2 * (N > 0 ? N : 1)); fixset = take(2 * (N > 0 ? N : 1));
-    Z = take(nf * ZS);      // the propagate's records (viekf_resident_common.hpp)
-    phiff = take(9 * (N > 0 ? N : 1));
-    // one region, two lives: the propagate's body-sized scratch | the update loop's column buffers
-    const int u0 = o;
-    Abb = take(256); Gb = take(96); Phibb = take(256); PhibbT = take(256); Gdb = take(96); T16 = take(256);
-    PsiP = take(ZK * 16); Pi = take(ZK * ZK); Xi = take(ZK * 16); AvG = take(18);
-    const int uprop = o;
-    o = u0;
-    Cb = take(4 * NQ);      // two buffers [NQ][2]: the column pair of the CURRENT measurement's feature, every pending update applied
-    Eb = take(4 * NQ);      // two buffers [NQ][2]: raw column pairs extracted from the tiles one update ahead
-    Pd = take(4 * (N > 0 ? N : 1));   // zeta-zeta 2x2 diagonal blocks, handed from the workers to the service lanes
-    if (uprop > o) o = uprop;
-    Mbb = take(256); Pbb = take(256);
-    xdb = take(16);
-    ctx = take((int)((sizeof(BodyCtx) + 7) / 8));
-    Pbc = take(nf * 16);    // the body columns P[16.., 0:16] during load and propagate (register tiles during the updates)
-    const int mc = res_mcap(N);
-    mslot = take(mc / 2); mseq = take(mc); mz = take(2 * mc); mR = take(4 * mc);
-    total = o;
-  }
-};
 
 struct TileShared : ResShared {   // (the propagate set-up routines of the resident family work on the ResShared part)
   double *Cb, *Eb;
@@ -88,7 +53,7 @@ __device__ __forceinline__ void tile_prologue(const StreamArgs& a, TileShared& S
                                               const int* __restrict__ slot_all, int M, int m_stride,
                                               const double* __restrict__ R_all, long r_stride_b, long r_stride_m,
                                               int* __restrict__ result_all) {
-  const TileLds L(a.N, a.n, a.nxs);
+  const TileLds L(a.N, a.n, a.nxs, sizeof(BodyCtx));
   S.xs = smem + L.xs; S.lam = smem + L.lam; S.sm = smem + L.sm; S.fixadd = smem + L.fixadd; S.fixset = smem + L.fixset;
   S.Z = smem + L.Z; S.phiff = smem + L.phiff; S.Abb = smem + L.Abb; S.Gb = smem + L.Gb; S.Phibb = smem + L.Phibb; S.Mbb = smem + L.Mbb;
   S.Gdb = smem + L.Gdb; S.Pbb = smem + L.Pbb; S.T16 = smem + L.T16; S.xdb = smem + L.xdb; S.Pbc = smem + L.Pbc; S.PhibbT = smem + L.PhibbT;
@@ -99,8 +64,8 @@ __device__ __forceinline__ void tile_prologue(const StreamArgs& a, TileShared& S
   S.mslot = reinterpret_cast<int*>(smem + L.mslot);
   S.mseq = reinterpret_cast<int2*>(smem + L.mseq);
   S.ctx = reinterpret_cast<BodyCtx*>(smem + L.ctx);
-  S.N = a.N; S.mcap = res_mcap(a.N); S.n = a.n; S.nf = 3 * a.N; S.len = present ? a.len[b] : 0; S.M = present ? M : 0; S.mstride = m_stride; S.do_prop = do_prop & 1;
-  S.dbg = (do_prop >> 8) & 0xff; S.kp = (do_prop >> 16) > 0 ? (do_prop >> 16) : 1; S.B = a.B; S.b = b; S.stamps = a.ws;
+  S.N = a.N; S.mcap = res_mcap(a.N); S.n = a.n; S.nf = 3 * a.N; S.len = present ? a.len[b] : 0; S.M = present ? M : 0; S.mstride = m_stride; S.do_prop = launch_prop(do_prop);
+  S.dbg = launch_dbg(do_prop); S.kp = launch_kp(do_prop); S.B = a.B; S.b = b; S.stamps = a.ws;
   S.NT = tile_nt(a.N); S.NQ = 16 * S.NT;
   S.si = present ? a.si(b) : 0; S.so = present ? a.so(b) : 0;
   if (present) {
@@ -108,7 +73,7 @@ __device__ __forceinline__ void tile_prologue(const StreamArgs& a, TileShared& S
     for (int i = tid; i < a.nxs; i += T) S.xs[i] = (i < xZ + 5 * S.len) ? xg[i] : 0.0;
     for (int i = tid; i < a.n; i += T) S.lam[i] = a.lambda[i];
     for (int i = tid; i < 2 * a.N; i += T) { S.fixadd[i] = 0.0; S.fixset[i] = 0.0; }
-    for (int i = tid; i < 64; i += T) S.sm[i] = (i == 42 && (do_prop & 1)) ? dt_all[b] : 0.0;
+    for (int i = tid; i < tile_sm::len(); i += T) S.sm[i] = (i == tile_sm::DT && launch_prop(do_prop)) ? dt_all[b] : 0.0;   // (all of it: tile_sm)
     for (int mm_ = tid; mm_ < M; mm_ += T) {
       const int slot = slot_all[(long)b * m_stride + mm_];
       const double z0 = z_all[((long)b * m_stride + mm_) * 2], z1 = z_all[((long)b * m_stride + mm_) * 2 + 1];
@@ -133,7 +98,7 @@ __device__ __forceinline__ void tile_prologue(const StreamArgs& a, TileShared& S
   if (tid == 0) {   // number of updates that will run (the paired kernel's two filters loop in step: the longer count rules)
     int c = 0;
     for (int i = 0; present && i < M; i++) c += S.mslot[i] >= 0;
-    S.sm[60] = (double)c;
+    S.sm[tile_sm::TRIPS] = (double)c;
   }
   __syncthreads();
 }

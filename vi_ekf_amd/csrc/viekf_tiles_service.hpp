@@ -22,7 +22,7 @@ __device__ __forceinline__ void tile_service(const StreamArgs& a, const TileShar
   const bool partial = prm.use_partial_update != 0;
   int par = 0;
   __builtin_amdgcn_s_setprio(3);   // the per-update critical path runs on this wave
-  double dt = sm[42];
+  double dt = sm[tile_sm::DT];
   RES_STAMP(S, lane == 0, 0);
   // dynamics of propagate kp (of S.kp): body Jacobian on lane 0 (+ A_v G_b for the workers' expansion of the feature rows), then
   // one feature per lane -- before B0, while the worker waves are still loading P from HBM
@@ -62,9 +62,9 @@ __device__ __forceinline__ void tile_service(const StreamArgs& a, const TileShar
 #pragma unroll
         for (int i = 0; i < 17; i++) xs[i] = xo[i];
       }
-      if (lane == 0) sm[40 + par] = 0.0;
+      if (lane == 0) sm[tile_sm::fix_word(par)] = 0.0;
       for (int f = lane; f < len; f += 64)   // fix_depth (vi_ekf.cpp:311): state here, covariance through the mailbox
-        res_fix_depth(xs + xZ + 5 * f, a.dp, &S.fixadd[par * N + f], &S.fixset[par * N + f], &sm[40 + par], &flag);
+        res_fix_depth(xs + xZ + 5 * f, a.dp, &S.fixadd[par * N + f], &S.fixset[par * N + f], &sm[tile_sm::fix_word(par)], &flag);
       par ^= 1;
       __syncthreads();  // B3p
       double dt_next = 0.0;
@@ -76,7 +76,7 @@ __device__ __forceinline__ void tile_service(const StreamArgs& a, const TileShar
       __syncthreads();  // B4p
       if (MP && kp + 1 < nkp) {
         dt = dt_next;
-        if (lane == 0) sm[42] = dt;
+        if (lane == 0) sm[tile_sm::DT] = dt;
         dyn_feat(dt);
       }
     }
@@ -142,8 +142,9 @@ __device__ __forceinline__ void tile_service(const StreamArgs& a, const TileShar
   };
   auto publish = [&](const Meas& q, int mbx) {
     if (lane == 0) {
-      double* d = sm + 8 * mbx;
-      d[0] = q.g00; d[1] = q.g01; d[2] = q.g11; d[3] = q.skip;
+      using namespace tile_sm;
+      double* d = sm + mbox(mbx);
+      d[MB_G00] = q.g00; d[MB_G01] = q.g01; d[MB_G11] = q.g11; d[MB_SKIP] = q.skip;
     }
   };
   // this lane's quaternion and linear state live in registers for the whole loop (written back once at the end)
@@ -175,7 +176,7 @@ __device__ __forceinline__ void tile_service(const StreamArgs& a, const TileShar
     const bool gated = cur.skip == 1.0;
     // NaN guard (vi_ekf_meas.cpp:247: a NaN in K or H skips the update, not fix_depth): K = C Hb^T S^-1 has one iff the column
     // pair or the measurement's 2x2 factors have one -- the worker threads test every row of the pair where they form it
-    const bool bad = cur.skip == 2.0 || sm[44 + cnt % 3] != 0.0;
+    const bool bad = cur.skip == 2.0 || sm[tile_sm::nan_word(cnt)] != 0.0;
     // correction lambda o (K r) = lambda o (C g_r)   (vi_ekf_meas.cpp:249-255)
     const double dv0 = lam0 * fma(c0.y, cur.gr1, c0.x * cur.gr0);
     const double dv1 = lam1 * fma(c1.y, cur.gr1, c1.x * cur.gr0);
@@ -200,13 +201,13 @@ __device__ __forceinline__ void tile_service(const StreamArgs& a, const TileShar
     }
     RES_STAMP(S, lane == 0 && cnt < 8, 16 + 4 * cnt + 1);
     if (PAIR) __syncthreads();   // mid-phase barrier of the pair (no data of this wave's depends on it)
-    if (lane == 0) sm[40 + par] = 0.0;
+    if (lane == 0) sm[tile_sm::fix_word(par)] = 0.0;
     // fix_depth (vi_ekf_meas.cpp:271; a gated update returns before it, :238): almost never fires -- one wave-wide test
     const bool odd_depth = !gated && isfeat && fid < len && !(lin >= 0.0 && lin <= 1e2);
     if (__any(odd_depth)) {
       if (odd_depth) {
-        fix_depth_rule(lin, rho_reset, flag, [&](double e2) { S.fixadd[par * N + fid] = e2; sm[40 + par] = 1.0; },
-                       [&] { S.fixset[par * N + fid] = 1.0; sm[40 + par] = 1.0; });
+        fix_depth_rule(lin, rho_reset, flag, [&](double e2) { S.fixadd[par * N + fid] = e2; sm[tile_sm::fix_word(par)] = 1.0; },
+                       [&] { S.fixset[par * N + fid] = 1.0; sm[tile_sm::fix_word(par)] = 1.0; });
       }
     }
     if (slot_next >= 0) {   // next measurement, from registers

@@ -162,7 +162,7 @@ __device__ __forceinline__ void tile_worker(const StreamArgs& a, const TileShare
   if (S.do_prop) {
     // per-lane parts of the operand addresses:  Dblk_T[row = l15][col = lg + 4 s4]  (block diagonal of the five Phi_ff of tile T:
     // phiff + 45 (T - 1) + 9 (l15 / 3) + 3 (l15 % 3) + col % 3) and the slot of a Z record that k = 4 k6 + lg of the K = 24
-    // coupling reads on either side (viekf_resident_common.hpp); the tile's part of an address is an immediate
+    // coupling reads on either side (viekf_fused_lds.hpp); the tile's part of an address is an immediate
     const int r3 = l15 / 3, rm = l15 - 3 * r3;
     for (int kp = 0; kp < nkp; kp++) {
       res_prop_setup<TW>(a, S, tid);   // (B1p, B2p, B2q inside)
@@ -237,7 +237,7 @@ __device__ __forceinline__ void tile_worker(const StreamArgs& a, const TileShare
       }
       __syncthreads();  // B4p
       for (int e = tid; e < 256; e += TW) { const int r = e >> 4, c = e & 15; Pbb[e] = S.Mbb[min(r, c) * 16 + max(r, c)]; }
-      if (MP && kp + 1 < nkp) apply_fixes(par ^ 1, S.sm[40 + (par ^ 1)]);
+      if (MP && kp + 1 < nkp) apply_fixes(par ^ 1, S.sm[tile_sm::fix_word(par ^ 1)]);
     }
     RES_STAMP(S, st0, 70);
     __syncthreads();  // B4q : the body block copy above is complete
@@ -304,7 +304,7 @@ __device__ __forceinline__ void tile_worker(const StreamArgs& a, const TileShare
   int m = __builtin_amdgcn_readfirstlane(res_next_valid(S, 0));
   int2 sq = uni2(S.mseq[min(m, S.mcap - 1)]);     // {index of the measurement after m, its slot}
   if (m < S.M) {
-    apply_fixes(par ^ 1, S.sm[40 + (par ^ 1)]);
+    apply_fixes(par ^ 1, S.sm[tile_sm::fix_word(par ^ 1)]);
     // hand the zeta-zeta 2x2 of every feature to the service lanes (they keep it current from here on): lower triangle, mirrored
     static_for<CNT>([&](auto sc) {
       constexpr int s = decltype(sc)::value, TI = Map::ti(W, s), TJ = Map::tj(W, s);
@@ -326,7 +326,7 @@ __device__ __forceinline__ void tile_worker(const StreamArgs& a, const TileShare
   __syncthreads();  // Bp : Pd and the first columns are published
   if (m < S.M && tid < NQ) {   // NaN in the first column pair (the later ones are tested where they are formed)
     const double2 c0 = lds_ld2(S.Cb + 2 * tid);
-    if (c0.x != c0.x || c0.y != c0.y) S.sm[44] = 1.0;
+    if (c0.x != c0.x || c0.y != c0.y) S.sm[tile_sm::nan_word(0)] = 1.0;
   }
   __syncthreads();  // B1 : the service published the first measurement's G and verdict
   RES_STAMP(S, st0, 73);
@@ -346,13 +346,13 @@ __device__ __forceinline__ void tile_worker(const StreamArgs& a, const TileShare
     if (PAIR && m >= S.M) { __syncthreads(); __syncthreads(); continue; }   // (done: keeps the other filter's barriers company)
     const int mnext = sq.x, snext = sq.y;
     const int2 sq2 = uni2(S.mseq[min(mnext, S.mcap - 1)]);
-    const double* mb = S.sm + 8 * (cnt & 1);
-    const double g00 = mb[0], g01 = mb[1], g11 = mb[2];
-    const bool run = mb[3] == 0.0 && S.sm[44 + cnt % 3] == 0.0 && !RES_ABLATE(S, 1);   // not gated, no NaN guard
-    const double fixpending = S.sm[40 + (par ^ 1)];
+    const double* mb = S.sm + tile_sm::mbox(cnt & 1);
+    const double g00 = mb[tile_sm::MB_G00], g01 = mb[tile_sm::MB_G01], g11 = mb[tile_sm::MB_G11];
+    const bool run = mb[tile_sm::MB_SKIP] == 0.0 && S.sm[tile_sm::nan_word(cnt)] == 0.0 && !RES_ABLATE(S, 1);   // not gated, no NaN guard
+    const double fixpending = S.sm[tile_sm::fix_word(par ^ 1)];
     const double* Cc = S.Cb + (cnt & 1) * 2 * NQ;
     double* Cn = S.Cb + ((cnt + 1) & 1) * 2 * NQ;
-    if (tid == 0) S.sm[44 + (cnt + 2) % 3] = 0.0;   // (the word of the phase after next: nobody reads or sets it in this phase)
+    if (tid == 0) S.sm[tile_sm::nan_word(cnt + 2)] = 0.0;   // (the word of the phase after next: nobody reads or sets it in this phase)
     apply_fixes(par ^ 1, fixpending);
     RES_STAMP(S, st0 && cnt < 8, 80 + 4 * cnt + 0);
     // (2) is spread over the MFMA sequence of (1): a wave issues in order, and a matrix instruction holds the next one back for
@@ -414,7 +414,7 @@ __device__ __forceinline__ void tile_worker(const StreamArgs& a, const TileShare
           if (fq == qs + 1) fe.x = alt;
           if (fix) {
             *reinterpret_cast<double2*>(Cn + 2 * fq) = fe;
-            if (fe.x != fe.x || fe.y != fe.y) S.sm[44 + (cnt + 1) % 3] = 1.0;
+            if (fe.x != fe.x || fe.y != fe.y) S.sm[tile_sm::nan_word(cnt + 1)] = 1.0;
           }
         }
         __builtin_amdgcn_sched_barrier(0);   // (keeps this placement: the scheduler would otherwise cluster loads and arithmetic)
@@ -422,7 +422,7 @@ __device__ __forceinline__ void tile_worker(const StreamArgs& a, const TileShare
     } else if (fix) {   // gated / NaN-guarded: nothing to apply, the raw pair is the current one
       const double2 e = lds_ld2(En + 2 * fq);
       *reinterpret_cast<double2*>(Cn + 2 * fq) = e;
-      if (e.x != e.x || e.y != e.y) S.sm[44 + (cnt + 1) % 3] = 1.0;
+      if (e.x != e.x || e.y != e.y) S.sm[tile_sm::nan_word(cnt + 1)] = 1.0;
     }
     RES_STAMP(S, st0 && cnt < 8, 80 + 4 * cnt + 1);
     RES_STAMP(S, st0 && cnt < 8, 80 + 4 * cnt + 2);
@@ -438,7 +438,7 @@ __device__ __forceinline__ void tile_worker(const StreamArgs& a, const TileShare
     m = mnext;
   }
   if (PAIR && !half) __syncthreads();
-  apply_fixes(par ^ 1, S.sm[40 + (par ^ 1)]);
+  apply_fixes(par ^ 1, S.sm[tile_sm::fix_word(par ^ 1)]);
   RES_STAMP(S, st0, 74);
 
   // ---------------- store: the lower triangle, straight from the tiles (lanes along the rows of P) ----------------
