@@ -1,0 +1,29 @@
+"""tests/test_suite_inventory.py guards the GPU tests listed in tests/golden/gpu_test_names.txt against disappearing unnoticed
+on a machine without a GPU.  The GPU tests of the body-only set-up on the service wave (tests/test_gpu_service_setup.py) are
+listed in a file of their own, tests/golden/gpu_service_setup_test_names.txt, and held to the same check here, with the same
+parser, as tests/test_setup_under_load_inventory.py does for its file: every listed function still exists and is still marked
+gpu, and the file has no test function that the list does not name."""
+import os
+
+from tests.test_suite_inventory import HERE, _test_functions
+
+LIST = os.path.join(HERE, "golden", "gpu_service_setup_test_names.txt")
+FILE = "tests/test_gpu_service_setup.py"
+
+
+def _listed():
+    with open(LIST) as fh:
+        return [ln.strip() for ln in fh if ln.strip() and not ln.startswith("#")]
+
+
+def test_every_listed_service_setup_gpu_test_still_exists():
+    names = _listed()
+    assert len(names) == len(set(names)) and len(names) >= 3
+    found = _test_functions(os.path.join(HERE, os.path.basename(FILE)))
+    for entry in names:
+        path, _, func = entry.partition("::")
+        assert path == FILE and func, "malformed entry %r" % entry
+        assert func in found, "listed GPU test no longer exists: %s" % entry
+        assert found[func], "listed GPU test is no longer marked gpu: %s" % entry
+    unlisted = sorted(set(found) - {e.partition("::")[2] for e in names})
+    assert not unlisted, "%s has tests that %s does not list: %s" % (FILE, LIST, unlisted)

@@ -32,6 +32,15 @@ print("service: B0 wait", d(0, 1), " body phase", d(1, 2), " B1p wait", d(2, 3),
 #  the set-up, `LDS part + issue->B0` does not contain their round trip and `wait for blocks` is what is left of it behind B3p.)
 print("worker : LDS part + issue->B0", d(63, 64), " B0 wait", d(64, 65), " set-up to B3p", d(65, 66), " B3p wait", d(66, 67),
       " wait for blocks", d(67, 74), " local3x3", d(74, 68), " GEMM", d(68, 69), " strips", d(69, 70), " B4p+extract->B1", d(70, 71))
+# The order of res_service_setup (the body-only set-up on the service wave): stamps 14 / 15 exist only there.  The service wave's
+# intervals are then  B1p -> body step + fix_depth (5 -> 6) -> stages (a), (b) of the body-only set-up (6 -> 14) -> B2p (14 -> 15) ->
+# Xi (15 -> 79) -> B3p (79 -> 7),  and the two lines above read: `B2p wait` = dynamics end -> B1p, `B3p wait` = everything from the
+# fix_depth pass to B3p.  Workers (both orders): 77 / 78 around B2p.
+if t[14]:
+    print("service (set-up on the service wave): after B1p: body step+fix", d(5, 6), " Phi_bb..Pi", d(6, 14), " B2p wait", d(14, 15),
+          " Xi", d(15, 79), " B3p wait", d(79, 7))
+if t[77]:
+    print("worker : B0 -> before B2p", d(65, 77), " B2p wait", d(77, 78), " B2p -> before B3p", d(78, 66))
 print("worker : B0 falls at", d(63, 65), " B3p falls at", d(63, 67), " blocks first used at", d(63, 74), " (ticks after the prologue)")
 # one barrier per update (B1).  service: 16+4it+{0: phase inputs loaded, 1: rotation vector ready, 2: gain rows of the next
 # measurement written (before B1), 3: after B1}; 128+4it+{0,1}: around the manifold correction.  worker (thread 0):

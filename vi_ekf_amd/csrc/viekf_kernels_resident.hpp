@@ -122,6 +122,7 @@ __global__ __launch_bounds__((NW + NS) * 64, (NW <= 3) ? 2 : 1) void k_step_resi
   }
 #endif
   constexpr bool BL = res_batched_loads(RB, NW);
+  constexpr bool SS = res_service_setup(RB, NW, MP);
   ResShared S;
   res_prologue<T, MP, BL>(a, S, smem, do_prop, dt_all, z_all, slot_all, M, m_stride, R_all, r_stride_b, r_stride_m, result_all);
   // The service wave's chain is the floor of an update, so it should not share its SIMD's issue slots with a worker wave.  A
@@ -130,11 +131,11 @@ __global__ __launch_bounds__((NW + NS) * 64, (NW <= 3) ? 2 : 1) void k_step_resi
   constexpr int SVC = (NW == 6 && NS == 1) ? 3 : NW;
   const int wave = tid >> 6;
   if (NS == 2) {
-    if (wave == NW) res_service<T, MP, 1, BL>(a, S, tid & 63, NW, u_all, dt_all, result_all);
-    else if (wave == NW + 1) res_service<T, MP, 2, BL>(a, S, tid & 63, NW, u_all, dt_all, result_all);
+    if (wave == NW) res_service<T, MP, 1, BL, SS>(a, S, tid & 63, NW, u_all, dt_all, result_all);
+    else if (wave == NW + 1) res_service<T, MP, 2, BL, SS>(a, S, tid & 63, NW, u_all, dt_all, result_all);
     else res_worker<RB, TW, MP, T, ZU, BL>(a, S, tid);
   } else {
-    if (wave == SVC) res_service<T, MP, 0, BL>(a, S, tid & 63, NW, u_all, dt_all, result_all);
+    if (wave == SVC) res_service<T, MP, 0, BL, SS>(a, S, tid & 63, NW, u_all, dt_all, result_all);
     else res_worker<RB, TW, MP, T, ZU, BL>(a, S, tid - (wave > SVC ? 64 : 0));
   }
 }

@@ -131,6 +131,28 @@ __device__ __forceinline__ void res_words(const int* __restrict__ resmap, int t,
 constexpr bool res_setup_under_load(int RB, int NW, bool MP) {
   return res_batched_loads(RB, NW) && !MP && ((NW == 3 && (RB == 4 || RB == 6 || RB == 7)) || (NW == 6 && RB == 5));
 }
+// Which kernels run the BODY-ONLY part of the propagate's set-up on the service wave (res_prop_setup_body_service,
+// viekf_resident_prop.hpp): Phi_bb / M_bb, Psi P_bb, T16, Gs_b, Pi and Xi involve the 16 x 16 body blocks alone, and between B1p and
+// B3p the service wave of a single-propagate kernel has nothing to do but the body state step and fix_depth.  With the gate on the
+// workers keep the expansion of the feature rows and V ([B1p..B2p]) and the Ut product ([B2p..B3p]); the barrier B2q is gone.  Every
+// element is the same expression on the same operands, so the results are bit for bit those of the old order.  The gate
+// covers the single-propagate kernels that run the set-up under the load (res_setup_under_load): there the workers reach B0 idle
+// and B3p is set by dynamics plus set-up -- <6,3>, <7,3> and <5,6>; <4,3> is gated off: its unit-Lambda step measured 1.0 % SLOWER,
+// beyond its spread, with its general-Lambda step and its propagate-only launch 0.7 - 1.0 % faster
+// (profiles/service_setup/instances_ab.md).  The multi-propagate kernels keep the old order -- their service wave fills this time
+// with the next propagate's body dynamics.  VIEKF_SERVICE_SETUP=0 at build time gives every kernel the old order, and a kernel
+// whose gate is off compiles to the instruction stream it had before.  VIEKF_SERVICE_SETUP_CHUNKS: where the third chunk of the
+// block loads is issued in the shorter set-up -- 1: behind a wave's first turn of the Ut product (the default: the headline step
+// measured -1.8 % against the parent with it, -1.2 % with 0), 0: behind B2p with the second (18 + 36 loads at 7 blocks per thread).
+#ifndef VIEKF_SERVICE_SETUP
+#define VIEKF_SERVICE_SETUP 1
+#endif
+#ifndef VIEKF_SERVICE_SETUP_CHUNKS
+#define VIEKF_SERVICE_SETUP_CHUNKS 1
+#endif
+constexpr bool res_service_setup(int RB, int NW, bool MP) {
+  return (VIEKF_SERVICE_SETUP) != 0 && res_setup_under_load(RB, NW, MP) && RB != 4;
+}
 // Which kernels ROTATE the operand reads of their sweeps under the multiply-adds (res_worker), a mask of parts:
 //   1  the update loop's block sweep: two operand buffers, block ia + 2's rows of K and W are read into the buffer block ia's
 //      multiply-adds just released -- L(0) L(1) F(0) L(2) F(1) ... F(RB - 1) -- instead of two blocks' reads, a wait, their

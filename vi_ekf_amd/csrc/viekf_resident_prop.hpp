@@ -112,6 +112,134 @@ __device__ RES_INLINE void res_fix_depth(double* xf, const DevParams* p, double*
 }
 
 
+// The six BODY-ONLY quantities of the set-up -- Phi_bb / M_bb, Psi P_bb, T16, Gs_b, Pi, Xi: they involve the 16 x 16 body blocks
+// alone, no feature row and no register block -- on the PRIMARY service wave (res_service_setup: the single-propagate kernels
+// that run the set-up under the load of P), which would otherwise only wait between B1p and B3p.
+// Every element is the expression the worker waves evaluate in the old order (res_prop_setup below), on the same operands, its sum
+// running k = 0 .. 15 in the same order; which lane evaluates an element, and what it evaluates next to it, does not enter its
+// value, so the two orders agree bit for bit (tests/test_gpu_service_setup.py).  What differs is how the sums are laid out in
+// time.  One wave has a third of the workers' lanes and so two to four elements of each quantity per lane: run one after the other,
+// each a chain of 16 dependent multiply-adds behind four exposed LDS round trips, the chain took longer than everything the workers
+// do meanwhile and the step got SLOWER (profiles/service_setup/README.md).  So the sums of ALL elements of a stage run side by
+// side (res_dots: one accumulator per element, k outermost): seven or eight independent chains share each round trip.  A lane whose
+// element takes no sum (the E_v / E_g rows of Psi) or does not exist runs its sum on clamped operands and drops the result.
+// The worker-side loops do NOT share this text: with calls to common per-element functions in place every kernel of the family,
+// the multi-propagate ones included, compiled to a different instruction stream (branch polarities of the three conditional
+// sums, index arithmetic of the <7,3> set-up), so the old statements stay where they stood -- a change to one of the six has to be
+// made in both places.
+template <int NE>
+__device__ __forceinline__ void res_dots(const double* const (&x)[NE], const double* const (&y)[NE], const int (&ys)[NE],
+                                         double (&acc)[NE]) {
+#pragma unroll
+  for (int j = 0; j < NE; j++) acc[j] = 0.0;
+#pragma unroll 4
+  for (int k = 0; k < 16; k++)
+#pragma unroll
+    for (int j = 0; j < NE; j++) acc[j] += x[j][k] * y[j][k * ys[j]];   // element j: sum_k x[k] y[k ys]
+}
+__device__ __forceinline__ int res_clamp3(int v) { return min(max(v, 0), 2); }
+// Stages (a) Phi_bb, M_bb, Phi_bb^T, Psi P_bb and (b) T16, Gs_b, Pi, ordered by wave_lds_sync (one wave: no barrier).  Everything
+// they read is in LDS by B1p (A_bb, G_b: this wave's dynamics; P_bb: loaded ahead of B0; sqrt(Qu): the prologue) and nothing they
+// write is touched by the workers' share of the interval (the expansion of the feature rows and V).  Pi must be complete at B2p,
+// ahead of the workers' Ut product.  LDSC: sqrt(Qu) from the LDS copy (see res_prop_setup).
+template <bool LDSC>
+__device__ __forceinline__ void res_prop_setup_body_service(const StreamArgs& a, const ResShared& S, int lane, double dt) {
+  const DevParams& prm = *a.dp;
+  {   // (a)  items 0..3: Phi_bb / M_bb element lane + 64 j;  4..6: Psi P_bb element lane + 64 (j - 4) < 144
+    const double* x[7]; const double* y[7];
+    const int ys[7] = {16, 16, 16, 16, 16, 16, 16};
+    double acc[7];
+#pragma unroll
+    for (int j = 0; j < 4; j++) { const int e = lane + 64 * j; x[j] = S.Abb + (e >> 4) * 16; y[j] = S.Abb + (e & 15); }
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+      const int e = lane + 64 * j, q = e >> 4;
+      x[4 + j] = S.Abb + (dxVEL + res_clamp3(q - 3)) * 16; y[4 + j] = S.Pbb + (e & 15);
+    }
+    res_dots<7>(x, y, ys, acc);
+#pragma unroll
+    for (int j = 0; j < 4; j++) {   // body transition blocks (vi_ekf.cpp:302-303)
+      const int e = lane + 64 * j, r = e >> 4, c = e & 15;
+      const double a2 = acc[j];
+      const double id = (r == c) ? 1.0 : 0.0, av = S.Abb[e];
+      S.Mbb[e] = id + av * (0.5 * dt) + a2 * (dt * dt * (1.0 / 6.0));
+      const double ph = id + av * dt + a2 * (0.5 * dt * dt);
+      S.Phibb[e] = ph;
+      S.PhibbT[c * 16 + r] = ph;
+    }
+#pragma unroll
+    for (int j = 0; j < 3; j++) {   // Psi P_bb: rows E_v, A_bb[vel rows], E_g of P_bb
+      const int e = lane + 64 * j, q = e >> 4, c = e & 15;
+      if (e < ZK * 16) {
+        double v;
+        if (q < 3) v = S.Pbb[(dxVEL + q) * 16 + c];
+        else if (q >= 6) v = S.Pbb[(dxB_G + q - 6) * 16 + c];
+        else v = acc[4 + j];
+        S.PsiP[e] = v;
+      }
+    }
+  }
+  wave_lds_sync();
+  {   // (b)  items 0..3: T16 element lane + 64 j;  4..5: Gs_b element lane + 64 (j - 4) < 96;  6..7: Pi element lane + 64 (j - 6) < 81
+    const double* x[8]; const double* y[8];
+    const int ys[8] = {16, 16, 16, 16, 6, 6, 1, 1};
+    double acc[8];
+#pragma unroll
+    for (int j = 0; j < 4; j++) { const int e = lane + 64 * j; x[j] = S.Phibb + (e >> 4) * 16; y[j] = S.Pbb + (e & 15); }
+#pragma unroll
+    for (int j = 0; j < 2; j++) { const int e = min(lane + 64 * j, 95); x[4 + j] = S.Mbb + (e / 6) * 16; y[4 + j] = S.Gb + e % 6; }
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+      const int e = min(lane + 64 * j, ZK * ZK - 1), q = e / ZK, jj = e - q * ZK;
+      x[6 + j] = S.PsiP + q * 16; y[6 + j] = S.Abb + (dxVEL + res_clamp3(jj - 3)) * 16;
+    }
+    res_dots<8>(x, y, ys, acc);
+#pragma unroll
+    for (int j = 0; j < 4; j++) S.T16[lane + 64 * j] = acc[j];
+#pragma unroll
+    for (int j = 0; j < 2; j++) {   // Gs_b = M_bb G_b dt sqrt(Qu)
+      const int e = lane + 64 * j, k = e % 6;
+      if (e < 96) S.Gdb[e] = acc[4 + j] * dt * (LDSC ? S.sm[res_sm::SQRTQU + k] : prm.sqrtQu[k]);
+    }
+#pragma unroll
+    for (int j = 0; j < 2; j++) {   // Pi = (Psi P_bb) Psi^T
+      const int e = lane + 64 * j, q = e / ZK, jj = e - q * ZK;
+      if (e < ZK * ZK) {
+        const double* pr = S.PsiP + q * 16;
+        double v;
+        if (jj < 3) v = pr[dxVEL + jj];
+        else if (jj >= 6) v = pr[dxB_G + jj - 6];
+        else v = acc[6 + j];
+        S.Pi[e] = v;
+      }
+    }
+  }
+}
+// Stage (c), Xi = Psi T16^T (T16^T = P_bb Phi_bb^T): nothing the workers read; T16, Xi, Gs_b and Phi_bb^T are read next by
+// res_prop_body, on this same wave, behind B3p.  Runs behind B2p (the workers' Ut product needs no part of it).
+__device__ __forceinline__ void res_prop_setup_xi_service(const ResShared& S, int lane) {
+  const double* x[3]; const double* y[3];
+  const int ys[3] = {1, 1, 1};
+  double acc[3];
+#pragma unroll
+  for (int j = 0; j < 3; j++) {
+    const int e = lane + 64 * j, q = e >> 4;
+    x[j] = S.Abb + (dxVEL + res_clamp3(q - 3)) * 16; y[j] = S.T16 + (e & 15) * 16;
+  }
+  res_dots<3>(x, y, ys, acc);
+#pragma unroll
+  for (int j = 0; j < 3; j++) {
+    const int e = lane + 64 * j, q = e >> 4, c = e & 15;
+    if (e < ZK * 16) {
+      double v;
+      if (q < 3) v = S.T16[c * 16 + dxVEL + q];
+      else if (q >= 6) v = S.T16[c * 16 + dxB_G + q - 6];
+      else v = acc[j];
+      S.Xi[e] = v;
+    }
+  }
+}
+
 // Propagate set-up on the worker waves (LDS only; see the header of this file for the algebra).  Three intervals:
 //   [B1p..B2p]  Phi_bb / M_bb, the per-feature expansion raw blocks -> D, Gs, V = Phi_ff P[feat, body] (in place), Psi P_bb
 //   [B2p..B2q]  Gs_b = M_bb G_b dt sqrt(Qu), T16 = Phi_bb P_bb, Pi = Psi P_bb Psi^T
@@ -120,8 +248,11 @@ __device__ RES_INLINE void res_fix_depth(double* xf, const DevParams* p, double*
 // LDSC: sqrt(Qu) from the resident family's LDS copy (res_sm::SQRTQU, viekf_fused_lds.hpp) -- read from memory, the constant's round
 // trip sits inside an interval the whole workgroup waits on, once per interval.  (The tile family's sm has no such words.)
 // hook(k), k = 0 .. 2 as std::integral_constant: called behind B1p, B2p and B2q (the worker's spread block loads)
+// SS (res_service_setup): the six body-only loops are the service wave's (res_prop_setup_body_service, _xi_service); two intervals are left,
+//   [B1p..B2p]  the per-feature expansion and V          [B2p..B3p]  Ut
+// B2q is gone on both sides; hook(0) is called behind B1p, hook(1) behind B2p and hook(2) where VIEKF_SERVICE_SETUP_CHUNKS says.
 struct ResNoHook { template <class K> __device__ __forceinline__ void operator()(K) const {} };
-template <int TW, bool LDSC = false, class Hook = ResNoHook>
+template <int TW, bool LDSC = false, class Hook = ResNoHook, bool SS = false>
 __device__ __forceinline__ void res_prop_setup(const StreamArgs& a, const ResShared& S, int tid, const Hook& hook = Hook()) {
   const int nf = S.nf, N = S.N;
   const DevParams& prm = *a.dp;
@@ -134,28 +265,30 @@ __device__ __forceinline__ void res_prop_setup(const StreamArgs& a, const ResSha
 
   // ---- [B1p..B2p]
   for (int e = tid; e < nf; e += TW) res_feature_expand_row(e / 3, e % 3, dt, Z, S.Gb, S.AvG, LDSC ? S.sm + res_sm::SQRTQU : prm.sqrtQu);
-  for (int e = TW - 1 - tid; e < 256; e += TW) {   // body transition blocks (vi_ekf.cpp:302-303), from the last threads
-    const int r = e >> 4, c = e & 15;
-    double a2 = 0.0;
+  if (!SS) {   // (SS: the service wave's, see res_prop_setup_body_service)
+    for (int e = TW - 1 - tid; e < 256; e += TW) {   // body transition blocks (vi_ekf.cpp:302-303), from the last threads
+      const int r = e >> 4, c = e & 15;
+      double a2 = 0.0;
 #pragma unroll 4
-    for (int k = 0; k < 16; k++) a2 += S.Abb[r * 16 + k] * S.Abb[k * 16 + c];
-    const double id = (r == c) ? 1.0 : 0.0, av = S.Abb[e];
-    Mbb[e] = id + av * (0.5 * dt) + a2 * (dt * dt * (1.0 / 6.0));
-    const double ph = id + av * dt + a2 * (0.5 * dt * dt);
-    Phibb[e] = ph;
-    S.PhibbT[c * 16 + r] = ph;   // transposed copy: lanes that differ in the OUTPUT column read consecutive words
-  }
-  for (int e = TW - 1 - tid; e < ZK * 16; e += TW) {   // Psi P_bb: rows E_v, A_bb[vel rows], E_g of P_bb
-    const int q = e >> 4, c = e & 15;
-    double v;
-    if (q < 3) v = Pbb[(dxVEL + q) * 16 + c];
-    else if (q >= 6) v = Pbb[(dxB_G + q - 6) * 16 + c];
-    else {
-      v = 0.0;
-#pragma unroll 4
-      for (int k = 0; k < 16; k++) v += S.Abb[(dxVEL + q - 3) * 16 + k] * Pbb[k * 16 + c];
+      for (int k = 0; k < 16; k++) a2 += S.Abb[r * 16 + k] * S.Abb[k * 16 + c];
+      const double id = (r == c) ? 1.0 : 0.0, av = S.Abb[e];
+      Mbb[e] = id + av * (0.5 * dt) + a2 * (dt * dt * (1.0 / 6.0));
+      const double ph = id + av * dt + a2 * (0.5 * dt * dt);
+      Phibb[e] = ph;
+      S.PhibbT[c * 16 + r] = ph;   // transposed copy: lanes that differ in the OUTPUT column read consecutive words
     }
-    S.PsiP[e] = v;
+    for (int e = TW - 1 - tid; e < ZK * 16; e += TW) {   // Psi P_bb: rows E_v, A_bb[vel rows], E_g of P_bb
+      const int q = e >> 4, c = e & 15;
+      double v;
+      if (q < 3) v = Pbb[(dxVEL + q) * 16 + c];
+      else if (q >= 6) v = Pbb[(dxB_G + q - 6) * 16 + c];
+      else {
+        v = 0.0;
+#pragma unroll 4
+        for (int k = 0; k < 16; k++) v += S.Abb[(dxVEL + q - 3) * 16 + k] * Pbb[k * 16 + c];
+      }
+      S.PsiP[e] = v;
+    }
   }
   for (int e = tid; e < 16 * N; e += TW) {   // V = Phi_ff[f] P[f, body], in place: item = (feature f, body column k)
     const int f = e >> 4, k = e & 15;
@@ -166,39 +299,43 @@ __device__ __forceinline__ void res_prop_setup(const StreamArgs& a, const ResSha
     pc[16] = ff[3] * p0 + ff[4] * p1 + ff[5] * p2;
     pc[32] = ff[6] * p0 + ff[7] * p1 + ff[8] * p2;
   }
+  RES_STAMP(S, tid == 0, 77);
   __syncthreads();  // B2p
+  RES_STAMP(S, tid == 0, 78);
   hook(std::integral_constant<int, 1>{});
 
   // ---- [B2p..B2q]
-  for (int e = tid; e < 256; e += TW) {
-    const int r = e >> 4, c = e & 15;
-    double sv = 0.0;
+  if (!SS) {
+    for (int e = tid; e < 256; e += TW) {
+      const int r = e >> 4, c = e & 15;
+      double sv = 0.0;
 #pragma unroll 4
-    for (int k = 0; k < 16; k++) sv += Phibb[r * 16 + k] * Pbb[k * 16 + c];
-    T16[e] = sv;
-  }
-  for (int e = TW - 1 - tid; e < 96; e += TW) {
-    const int r = e / 6, k = e % 6;
-    double sv = 0.0;
-#pragma unroll 4
-    for (int c = 0; c < 16; c++) sv += Mbb[r * 16 + c] * S.Gb[c * 6 + k];
-    Gdb[e] = sv * dt * (LDSC ? S.sm[res_sm::SQRTQU + k] : prm.sqrtQu[k]);
-  }
-  for (int e = tid; e < ZK * ZK; e += TW) {   // Pi = (Psi P_bb) Psi^T
-    const int q = e / ZK, j = e - q * ZK;
-    const double* pr = S.PsiP + q * 16;
-    double v;
-    if (j < 3) v = pr[dxVEL + j];
-    else if (j >= 6) v = pr[dxB_G + j - 6];
-    else {
-      v = 0.0;
-#pragma unroll 4
-      for (int k = 0; k < 16; k++) v += pr[k] * S.Abb[(dxVEL + j - 3) * 16 + k];
+      for (int k = 0; k < 16; k++) sv += Phibb[r * 16 + k] * Pbb[k * 16 + c];
+      T16[e] = sv;
     }
-    S.Pi[e] = v;
+    for (int e = TW - 1 - tid; e < 96; e += TW) {
+      const int r = e / 6, k = e % 6;
+      double sv = 0.0;
+#pragma unroll 4
+      for (int c = 0; c < 16; c++) sv += Mbb[r * 16 + c] * S.Gb[c * 6 + k];
+      Gdb[e] = sv * dt * (LDSC ? S.sm[res_sm::SQRTQU + k] : prm.sqrtQu[k]);
+    }
+    for (int e = tid; e < ZK * ZK; e += TW) {   // Pi = (Psi P_bb) Psi^T
+      const int q = e / ZK, j = e - q * ZK;
+      const double* pr = S.PsiP + q * 16;
+      double v;
+      if (j < 3) v = pr[dxVEL + j];
+      else if (j >= 6) v = pr[dxB_G + j - 6];
+      else {
+        v = 0.0;
+#pragma unroll 4
+        for (int k = 0; k < 16; k++) v += pr[k] * S.Abb[(dxVEL + j - 3) * 16 + k];
+      }
+      S.Pi[e] = v;
+    }
+    __syncthreads();  // B2q
   }
-  __syncthreads();  // B2q
-  hook(std::integral_constant<int, 2>{});
+  if (!SS || VIEKF_SERVICE_SETUP_CHUNKS == 0) hook(std::integral_constant<int, 2>{});
 
   // ---- [B2q..B3p]
   // Ut = [D | V] [Pi / 2 ; Psi^T]  (nf x 25)(25 x 9) on the matrix cores, one 16-row tile per wave and turn, 7 k-steps (as
@@ -234,19 +371,23 @@ __device__ __forceinline__ void res_prop_setup(const StreamArgs& a, const ResSha
         const int row = 16 * t + lk + 4 * r4;
         if (row < nf && lr < ZK) Z[row * ZS + 2 * lr] = acc[r4];
       }
+      if (SS && VIEKF_SERVICE_SETUP_CHUNKS == 1 && t == wv) hook(std::integral_constant<int, 2>{});   // behind the first turn
     }
+    if (SS && VIEKF_SERVICE_SETUP_CHUNKS == 1 && wv * 16 >= nf) hook(std::integral_constant<int, 2>{});   // (a wave without a turn)
   }
-  for (int e = TW - 1 - tid; e < ZK * 16; e += TW) {   // Xi = Psi T16^T  (T16^T = P_bb Phi_bb^T)
-    const int q = e >> 4, c = e & 15;
-    double v;
-    if (q < 3) v = T16[c * 16 + dxVEL + q];
-    else if (q >= 6) v = T16[c * 16 + dxB_G + q - 6];
-    else {
-      v = 0.0;
+  if (!SS) {
+    for (int e = TW - 1 - tid; e < ZK * 16; e += TW) {   // Xi = Psi T16^T  (T16^T = P_bb Phi_bb^T)
+      const int q = e >> 4, c = e & 15;
+      double v;
+      if (q < 3) v = T16[c * 16 + dxVEL + q];
+      else if (q >= 6) v = T16[c * 16 + dxB_G + q - 6];
+      else {
+        v = 0.0;
 #pragma unroll 4
-      for (int k = 0; k < 16; k++) v += S.Abb[(dxVEL + q - 3) * 16 + k] * T16[c * 16 + k];
+        for (int k = 0; k < 16; k++) v += S.Abb[(dxVEL + q - 3) * 16 + k] * T16[c * 16 + k];
+      }
+      S.Xi[e] = v;
     }
-    S.Xi[e] = v;
   }
 }
 

@@ -11,7 +11,10 @@ namespace viekf {
 // (N <= 114 by lanes; the register file ends the family at N = 72), features 64.. on its lanes 14...  A measurement is
 // predicted by the wave that holds its feature; the other one receives {Hb, residual, S^-1, gate} through an LDS mailbox
 // (polled; bounded); each wave writes the gain rows, the NaN-guard word and the fix_depth mailbox flag of its own rows.
-template <int T, bool MP, int ROLE = 0, bool BL = true>
+// SS (res_service_setup, single-propagate kernels only): between B1p and B2p the PRIMARY wave runs the body state step, fix_depth
+// and the body-only part of the propagate's set-up that the workers' Ut product waits for (res_prop_setup_body_service), between
+// B2p and B3p the rest of it (Xi); the barrier B2q does not exist.
+template <int T, bool MP, int ROLE = 0, bool BL = true, bool SS = false>
 __device__ __forceinline__ void res_service(const StreamArgs& a, const ResShared& S, int lane, int nww,
                                             const double* __restrict__ u_all, const double* __restrict__ dt_all,
                                             int* __restrict__ result_all) {
@@ -60,9 +63,13 @@ __device__ __forceinline__ void res_service(const StreamArgs& a, const ResShared
    for (int kp = 0; kp < nkp; kp++) {
     __syncthreads();  // B1p
     RES_STAMP(S, lane == 0, 3);
-    __syncthreads();  // B2p
-    __syncthreads();  // B2q
+    if (!SS) {
+      __syncthreads();  // B2p
+      __syncthreads();  // B2q
+    }
     RES_STAMP(S, lane == 0, 5);
+    // (SS: both depend on nothing the workers do since B0, and nothing they write -- the state, the fix mailbox -- is read by a
+    //  worker before B4p)
     if (PRIMARY && lane == 63) {   // body state step (every feature lane has consumed the old body state through ctx)
       double dxb[16], xo[17];
 #pragma unroll
@@ -76,6 +83,15 @@ __device__ __forceinline__ void res_service(const StreamArgs& a, const ResShared
       res_fix_depth(xs + xZ + 5 * f, a.dp, &S.fixadd[par * N + f], &S.fixset[par * N + f], &sm[res_sm::fix_word(ROLE, par)], &flag);
     par ^= 1;
     RES_STAMP(S, lane == 0, 6);
+    if (SS) {
+      static_assert(!SS || !MP, "the service-side set-up is the single-propagate kernels'");
+      if (PRIMARY) res_prop_setup_body_service<BL>(a, S, lane, dt);
+      RES_STAMP(S, lane == 0, 14);
+      __syncthreads();  // B2p : Pi is complete (the workers' Ut product reads it)
+      RES_STAMP(S, lane == 0, 15);
+      if (PRIMARY) res_prop_setup_xi_service(S, lane);
+      RES_STAMP(S, lane == 0, 79);
+    }
     __syncthreads();  // B3p
     RES_STAMP(S, lane == 0, 7);
     // Several propagates per launch: the body part of the NEXT one's dynamics runs here, under the workers' contraction (this

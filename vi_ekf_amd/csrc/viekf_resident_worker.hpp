@@ -127,7 +127,8 @@ __device__ __forceinline__ void res_body_items(const ResShared& S, const double*
 // BL: the instance issues its launch-constant loads in batches (res_batched_loads, viekf_fused_lds.hpp)
 // SU: the block loads of P are in flight across B0 and the propagate's set-up (res_setup_under_load, same file), and their issue is
 //     spread over the set-up's barrier intervals: chunk k of 4 = blocks [RB k / 4, RB (k + 1) / 4), chunk 0 ahead of B0, chunks 1 .. 3
-//     behind B1p, B2p and B2q (the hook of res_prop_setup) -- with all of them issued at once a wave stands at the issue while the
+//     behind B1p, B2p and B2q (the hook of res_prop_setup; where B2q is gone -- res_service_setup -- chunk 3 follows a wave's first
+//     turn of the Ut product: VIEKF_SERVICE_SETUP_CHUNKS) -- with all of them issued at once a wave stands at the issue while the
 //     memory system works off the batch of every workgroup on the chip.  Everything the set-up reads is in LDS before the first of
 //     them is issued, and nothing between that and the barrier B3p touches `pb` or waits for a vector memory instruction younger
 //     than the ownership words -- loads return in order, so a wait for any later one would drain them
@@ -331,7 +332,7 @@ __device__ __forceinline__ void res_worker(const StreamArgs& a, const ResShared&
     // (multi-propagate instances: sqrt(Qu) stays a memory operand of the set-up -- cached after the first propagate; the LDS
     //  operand cost them 16 .. 22 scalar-register reloads per update in the service loop)
     if (MP || !BL) res_prop_setup<TW>(a, S, tk);
-    else if (SU) res_prop_setup<TW, true>(a, S, tk, issue_chunk);
+    else if (SU) res_prop_setup<TW, true, decltype(issue_chunk), res_service_setup(RB, TW / 64, MP)>(a, S, tk, issue_chunk);
     else res_prop_setup<TW, true>(a, S, tk);
     RES_STAMP(S, tid == 0, 66);
     __syncthreads();  // B3p
