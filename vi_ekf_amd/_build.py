@@ -18,6 +18,7 @@ def sources():
     out.append(os.path.join(os.path.dirname(HERE), "include", "viekf_map.h"))
     out.append(os.path.join(os.path.dirname(HERE), "include", "viekf_rec.h"))
     out.append(os.path.join(os.path.dirname(HERE), "include", "viekf_cam.h"))
+    out.append(os.path.join(os.path.dirname(HERE), "include", "viekf_body.h"))
     return out
 
 

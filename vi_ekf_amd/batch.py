@@ -203,6 +203,56 @@ class BatchVIEKF:
         self._keep = []
         return res
 
+    def update_body(self, entries, active=None, result=None):
+        """The body-sensor updates of one tick, in order, in one pass over P (viekf_batch_update_body, include/viekf_body.h).
+        entries: a list of (mtype, z, R) with mtype ACC / ALT / ATT / POS / VEL, z [B][zdim] and R (rdim, rdim) shared by the
+        filters or (B, rdim, rdim) -- all entries the same way -- as numpy arrays; or, for device memory, the tuple
+        (types, zdim, rdim, z, R) with types / zdim / rdim as sequences of M ints and z [M][B][4], R [M][9] or [M][B][9]
+        (each R column-major in its cell) as CUDA tensors.  active [M][B] (0 / 1 / 2 as update()) or None.
+        -> (result [M][B], route): route 1 = the fused launch, 0 = M launches of update()'s kernel"""
+        self._keep = []
+        if isinstance(entries, tuple):
+            types, zdim, rdim, z, R = entries
+            M = len(types)
+        else:
+            M = len(entries)
+            types, zdim, rdim = [], [], []
+            z = np.zeros((M, self.B, 4))
+            per_filter = [np.asarray(e[2]).ndim == 3 for e in entries]
+            if any(per_filter) != all(per_filter):
+                raise ValueError("R must be shared in every entry or per filter in every entry")
+            R = np.zeros((M, self.B, 9) if M and per_filter[0] else (M, 9))
+            for m, (mtype, zm, Rm) in enumerate(entries):
+                zm = np.asarray(zm, dtype=np.float64)
+                Rm = np.asarray(Rm, dtype=np.float64)
+                if zm.ndim != 2 or zm.shape[0] != self.B or not 1 <= zm.shape[1] <= 4:
+                    raise ValueError("z of entry %d must be [B][zdim], zdim 1..4" % m)
+                if Rm.shape[-1] != Rm.shape[-2] or not 1 <= Rm.shape[-1] <= 3 or (Rm.ndim == 3 and Rm.shape[0] != self.B):
+                    raise ValueError("R of entry %d must be (rdim, rdim) or (B, rdim, rdim), rdim 1..3" % m)
+                r = Rm.shape[-1]
+                types.append(int(mtype)); zdim.append(zm.shape[1]); rdim.append(r)
+                z[m, :, :zm.shape[1]] = zm
+                R[m, ..., :r * r] = np.swapaxes(Rm, -1, -2).reshape(Rm.shape[:-2] + (r * r,))
+        if not (len(types) == len(zdim) == len(rdim) == M):
+            raise ValueError("types, zdim and rdim must have one value per entry")
+        r_mode = 1 if len(R.shape) == 3 else 0
+        ty, zd, rd = (np.ascontiguousarray(v, dtype=np.int32) for v in (types, zdim, rdim))
+        pz, w = self._arg(z, np.float64, (M, self.B, 4), None)
+        pR, w = self._arg(R, np.float64, (M, self.B, 9) if r_mode else (M, 9), w)
+        pa, w = self._arg(active, np.uint8, (M, self.B), w)
+        if result is None:
+            if w == capi.DEVICE:
+                import torch
+                result = torch.empty((M, self.B), dtype=torch.int32, device=z.device)
+            else:
+                result = np.empty((M, self.B), dtype=np.int32)
+        pres, w = self._out(result, np.int32, (M, self.B), w)
+        route = C.c_int32(-1)
+        capi.check(capi.lib().viekf_batch_update_body(self._h, M, C.c_void_p(ty.ctypes.data), C.c_void_p(zd.ctypes.data),
+                                                      C.c_void_p(rd.ctypes.data), pz, pR, r_mode, pa, pres, C.byref(route), w))
+        self._keep = []
+        return result, route.value
+
     def keep_features(self, keep):
         """drop the features with keep[b, f] == 0 and compact (reference vi_ekf_feat.cpp:50-117) -> new len [B]"""
         self._keep = []

@@ -37,6 +37,10 @@ SYMBOLS = [
     "viekf_batch_select_filters", "viekf_batch_propagate_filters_to", "viekf_batch_propagate_n_filters_to",
 ]
 
+# what include/viekf_body.h declares (the fused body-sensor update: BatchVIEKF.update_body)
+BODY_SYMBOLS = ["viekf_batch_update_body", "viekf_body_lds_bytes", "viekf_body_lds_limit"]
+BODY_MAX_M = 8
+
 
 class Params(C.Structure):
     """struct viekf_params (include/viekf.h) == the keys VIEKF::load reads (reference vi_ekf.cpp:114-131)."""
@@ -159,6 +163,10 @@ def lib():
         L.viekf_frame_set_tracked.argtypes = [_vp, _vp, C.c_int]
         L.viekf_frame_tracked.argtypes = [_vp, _vp, _vp, C.c_int]
         L.viekf_frame_intake.argtypes = [_vp, C.c_int32, _vp, _vp, _vp, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int]
+        L.viekf_batch_update_body.argtypes = [_vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.c_int32, _vp, _vp, C.POINTER(C.c_int32), C.c_int]
+        L.viekf_body_lds_bytes.argtypes = [C.c_int32, C.c_int32]
+        L.viekf_body_lds_bytes.restype = C.c_int64
+        L.viekf_body_lds_limit.argtypes = [C.c_int32, C.POINTER(C.c_int64)]
         _lib = L
     return _lib
 

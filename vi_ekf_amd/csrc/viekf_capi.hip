@@ -1009,6 +1009,7 @@ int viekf_batch_step_n(viekf_batch* b, int32_t K, const double* u, const double*
 }  // extern "C"
 
 // the companions of a batch, each with its handle and helpers (still this one translation unit)
+#include "viekf_capi_body.hpp"
 #include "viekf_capi_diag.hpp"
 #include "viekf_capi_frame.hpp"
 #include "viekf_capi_node.hpp"
