@@ -2,8 +2,8 @@
 
 The small parity tests (tests/test_gpu_parity.py, B <= 12) only ever exercise the first workgroup
 that lands on a CU.  The headline runs 1024 workgroups over 256 CUs (four rounds; a later workgroup
-starts on LDS / registers that still hold a previous filter's data), and the two-per-CU instance
-<3,2> is only picked when the batch exceeds the CU count.  Here the HIP path runs the full batch
+starts on LDS / registers that still hold a previous filter's data), and the two- and four-per-CU
+instances <2,1>, <2,2> and <3,2> are only picked when the batch exceeds the CU count.  Here the HIP path runs the full batch
 and a strided sample of filters -- first, last and the ones either side of a round boundary -- is
 compared with the CPU oracle on the same seeded inputs, with the same bar as test_gpu_parity.py.
 
@@ -18,6 +18,7 @@ import pytest
 import vi_ekf_amd as v
 from oracle import oracle as orc
 from vi_ekf_amd import scene
+from tests import hetero_cases as hc
 from tests.test_gpu_parity import assert_close, oracle_params
 
 pytestmark = pytest.mark.gpu
@@ -38,6 +39,14 @@ def oracle_subset(sc, N, steps, which):
     return np.stack([f.x.copy() for f in fs]), np.stack([f.P.copy() for f in fs]), res
 
 
+def expected_instance(B, N):
+    """what describe() must name for an automatic batch on this device: the row of kResInst that setup_resident's rule picks
+    (the table itself, read by tests/hetero_cases.py, and the device's CU count), or the streaming family past its last row"""
+    import torch
+    row = hc.auto_row(N, B, torch.cuda.get_device_properties(0).multi_processor_count)
+    return hc.row_name(row) if row >= 0 else "k_propagate_"
+
+
 def run_full(B, N, steps, which, kernel=0, seed=None, tune=()):
     sc = scene.make_scene(B, N, steps, seed=4000 + N if seed is None else seed)
     g = v.BatchVIEKF(B, N, sc["params"])
@@ -45,6 +54,8 @@ def run_full(B, N, steps, which, kernel=0, seed=None, tune=()):
         g.set_kernel(kernel)
     for key, value in tune:
         g.set_tuning(key, value)
+    if kernel == 0:
+        assert g.describe().startswith(expected_instance(B, N)), (g.describe(), expected_instance(B, N))
     for i in range(N):
         ok = g.init_feature(sc["pix"][:, i, :].copy(), np.full(B, np.nan))
         assert (ok == 1).all()
@@ -71,9 +82,11 @@ def test_headline_batch_every_dispatch_round():
     run_full(1024, 50, 3, [0, 255, 256, 511, 700, 1023])
 
 
-@pytest.mark.parametrize("N", [12, 20])
+@pytest.mark.parametrize("N", [12, 20, 25])
 def test_two_per_cu_instance_beyond_one_round(N):
-    """B=600 > 256 CUs: the <3,2> instance (192 threads, two workgroups per CU) is the one picked"""
+    """B=600 > 256 CUs: by the table, on a 256-CU device N = 12 runs on <2,1> (four 128-thread workgroups per CU: 600 > 2 x 256),
+    N = 20 on <2,2> and N = 23 .. 25 on <3,2> (192 threads), both two workgroups per CU; run_full asserts the instance that
+    describe() names against the table and the device's CU count"""
     run_full(600, N, 4, [0, 1, 255, 256, 511, 512, 598, 599])
 
 
