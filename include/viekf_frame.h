@@ -82,7 +82,9 @@ int viekf_frame_tracked(viekf_frame *f, int32_t *ids, int32_t *len, viekf_mem wh
  * VIEKF_MEAS_INVALID (viekf_frame_set_tracked adopts the new state).
  * Inactive filters are untouched: results VIEKF_MEAS_SKIPPED, gated_count 0, did_reset 0.
  * Ring slots selected with viekf_batch_select / viekf_batch_select_filters are followed.  A participation mask
- * (viekf_batch_set_active) in force is refused with VIEKF_ERR_INVALID: the call has its own. */
+ * (viekf_batch_set_active) in force is refused with VIEKF_ERR_INVALID: the call has its own.
+ * The frame's DEPTH measurements (:301-303) are a call of their own behind this one, with this call's ids and result: the
+ * intake's depth step, declared in viekf_depth.h beside the update it runs on. */
 int viekf_frame_intake(viekf_frame *f, int32_t M, const double *z, const int32_t *ids, const double *depth, const double *R,
                        int32_t r_mode, const uint8_t *active, int32_t *result, int32_t *gated, int32_t *gated_count,
                        uint8_t *did_reset, double *edges, viekf_mem where);

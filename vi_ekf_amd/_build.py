@@ -19,6 +19,7 @@ def sources():
     out.append(os.path.join(os.path.dirname(HERE), "include", "viekf_rec.h"))
     out.append(os.path.join(os.path.dirname(HERE), "include", "viekf_cam.h"))
     out.append(os.path.join(os.path.dirname(HERE), "include", "viekf_body.h"))
+    out.append(os.path.join(os.path.dirname(HERE), "include", "viekf_depth.h"))
     return out
 
 

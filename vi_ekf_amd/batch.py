@@ -253,6 +253,45 @@ class BatchVIEKF:
         self._keep = []
         return result, route.value
 
+    def update_depths(self, mtype, z, slot, R, active=None, order=0, result=None):
+        """M DEPTH (or INV_DEPTH) updates per filter in one pass over P (viekf_batch_update_depths, include/viekf_depth.h).
+        mtype DEPTH or INV_DEPTH; z [B][M], slot [B][M] (a slot may repeat; -1 = no entry); R the variance: a float, [B] or
+        [B][M]; active [B][M] (0 / 1 / 2 as update()) or None; order 0 = entry 0 first, 1 = entry M-1 first (the
+        reference's queue order within a stamp).  numpy arrays, or contiguous CUDA tensors (R then a tensor of shape (1,),
+        (B,) or (B, M)) -- one call takes one kind.
+        -> (result [B][M], route): route 1 = the fused launch, 0 = M launches of update()'s kernel"""
+        self._keep = []
+        if len(slot.shape) != 2:
+            raise ValueError("slot must be [B][M]")
+        M = int(slot.shape[1])
+        if not is_torch(R):
+            R = np.asarray(R, dtype=np.float64)
+            if is_torch(z):                                    # (a plain number beside device tensors)
+                import torch
+                R = torch.as_tensor(R, dtype=torch.float64, device=z.device).contiguous()
+                self._depths_R = R                             # (must outlive the queued work: kept until the next call)
+        r_mode = {(): 0, (1,): 0, (self.B,): 1, (self.B, M): 2}.get(tuple(R.shape))
+        if r_mode is None:
+            raise ValueError("R must be a scalar, [B] or [B][M]")
+        if r_mode == 0:
+            R = R.reshape(1)
+        ps, w = self._arg(slot, np.int32, (self.B, M), None)
+        pz, w = self._arg(z, np.float64, (self.B, M), w)
+        pR, w = self._arg(R, np.float64, tuple(R.shape), w)
+        pa, w = self._arg(active, np.uint8, (self.B, M), w)
+        if result is None:
+            if w == capi.DEVICE:
+                import torch
+                result = torch.empty((self.B, M), dtype=torch.int32, device=z.device)
+            else:
+                result = np.empty((self.B, M), dtype=np.int32)
+        pres, w = self._out(result, np.int32, (self.B, M), w)
+        route = C.c_int32(-1)
+        capi.check(capi.lib().viekf_batch_update_depths(self._h, int(mtype), M, ps, pz, pR, r_mode, pa, int(order), pres,
+                                                        C.byref(route), w))
+        self._keep = []
+        return result, route.value
+
     def keep_features(self, keep):
         """drop the features with keep[b, f] == 0 and compact (reference vi_ekf_feat.cpp:50-117) -> new len [B]"""
         self._keep = []

@@ -41,6 +41,11 @@ SYMBOLS = [
 BODY_SYMBOLS = ["viekf_batch_update_body", "viekf_body_lds_bytes", "viekf_body_lds_limit"]
 BODY_MAX_M = 8
 
+# what include/viekf_depth.h declares (a frame's DEPTH updates in one launch: BatchVIEKF.update_depths; the intake's depth
+# step: FrameIntake.intake_depth)
+DEPTH_SYMBOLS = ["viekf_batch_update_depths", "viekf_depths_lds_bytes", "viekf_frame_intake_depth"]
+DEPTHS_MAX_M = 256
+
 
 class Params(C.Structure):
     """struct viekf_params (include/viekf.h) == the keys VIEKF::load reads (reference vi_ekf.cpp:114-131)."""
@@ -167,6 +172,10 @@ def lib():
         L.viekf_body_lds_bytes.argtypes = [C.c_int32, C.c_int32]
         L.viekf_body_lds_bytes.restype = C.c_int64
         L.viekf_body_lds_limit.argtypes = [C.c_int32, C.POINTER(C.c_int64)]
+        L.viekf_batch_update_depths.argtypes = [_vp, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int32, _vp, C.c_int32, _vp, C.POINTER(C.c_int32), C.c_int]
+        L.viekf_depths_lds_bytes.argtypes = [C.c_int32, C.c_int32]
+        L.viekf_depths_lds_bytes.restype = C.c_int64
+        L.viekf_frame_intake_depth.argtypes = [_vp, C.c_int32, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, _vp, _vp, C.c_int]
         _lib = L
     return _lib
 

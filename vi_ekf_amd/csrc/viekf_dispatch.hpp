@@ -11,6 +11,7 @@
 #include "viekf_batch.hpp"
 #include "viekf_instances.hpp"
 #include "viekf_kernels_body.hpp"
+#include "viekf_kernels_depth.hpp"
 #include "viekf_kernels_generic.hpp"
 #include "viekf_kernels_hooks.hpp"
 #include "viekf_kernels_lifecycle.hpp"

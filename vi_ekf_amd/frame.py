@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-from ._dev import Companion, r_colmajor
+from ._dev import Companion, is_torch, r_colmajor
 
 # every symbol include/viekf_frame.h declares (tests check the library exports exactly these)
 FRAME_SYMBOLS = ["viekf_frame_create", "viekf_frame_destroy", "viekf_frame_reset", "viekf_frame_set_tracked",
@@ -93,3 +93,38 @@ class FrameIntake(Companion):
             self._pending = (z, ids, Rc, depth, active)   # (re-laid-out R must outlive the queued work)
         self._done(dev, sync)
         return out
+
+    def intake_depth(self, out_or_result, ids, depth, R, use_depth=True, active=None):
+        """the frame's DEPTH measurements, behind intake() of the same frame (viekf_frame_intake_depth, include/viekf_depth.h):
+        out_or_result = what intake() returned, or its "result" [B][M]; ids [B][M] and depth [B][M] as given to intake();
+        R the DEPTH variance: a float, [B] or [B][M]; use_depth False = inactive measurements (fix_depth only); active [B]
+        uint8 or None -> result [B][M], where the inputs live"""
+        g = self.batch
+        h = self._handle()
+        g._keep = []
+        B = g.B
+        fres = out_or_result["result"] if isinstance(out_or_result, dict) else out_or_result
+        if len(ids.shape) != 2:
+            raise ValueError("ids must be [B][M]")
+        M = int(ids.shape[1])
+        if not is_torch(R):
+            R = np.asarray(R, dtype=np.float64)
+            if is_torch(depth):                                # (a plain number beside device tensors)
+                import torch
+                R = torch.as_tensor(R, dtype=torch.float64, device=depth.device).contiguous()
+        r_mode = {(): 0, (1,): 0, (B,): 1, (B, M): 2}.get(tuple(R.shape))
+        if r_mode is None:
+            raise ValueError("R must be a scalar, [B] or [B][M]")
+        if r_mode == 0:
+            R = R.reshape(1)
+        pi, w = g._arg(ids, np.int32, (B, M), None)
+        pd, w = g._arg(depth, np.float64, (B, M), w)
+        pf, w = g._arg(fres, np.int32, (B, M), w)
+        pR, w = g._arg(R, np.float64, tuple(R.shape), w)
+        pa, w = g._arg(active, np.uint8, (B,), w)
+        dev = w == capi.DEVICE
+        result, pres = self._empty((B, M), np.int32, dev)
+        self._ready(dev, True)
+        capi.check(self._L.viekf_frame_intake_depth(h, M, pi, pd, pf, pR, r_mode, 1 if use_depth else 0, pa, pres, w))
+        self._done(dev, True)
+        return result
