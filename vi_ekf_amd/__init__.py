@@ -5,6 +5,14 @@ does not need a GPU; using it does, and there is no CPU fallback.
 """
 from . import capi, scene  # noqa: F401
 from .batch import BatchVIEKF  # noqa: F401
+
+
+def pixel_flow(batch, z_prev, ids_prev, z, ids, dt):
+    """the image velocity of a frame's features from the frame before, by id, on the batch's stream (viekf_pixel_flow,
+    include/viekf_pixvel.h) -> zdot [B][M][2]"""
+    return batch.pixel_flow(z_prev, ids_prev, z, ids, dt)
+
+
 from .capi import Params, ViekfError, device_count, load_yaml  # noqa: F401
 from .seq import SeqVIEKF  # noqa: E402,F401
 from .klt import KLTTracker, track_frame  # noqa: E402,F401

@@ -20,6 +20,7 @@ def sources():
     out.append(os.path.join(os.path.dirname(HERE), "include", "viekf_cam.h"))
     out.append(os.path.join(os.path.dirname(HERE), "include", "viekf_body.h"))
     out.append(os.path.join(os.path.dirname(HERE), "include", "viekf_depth.h"))
+    out.append(os.path.join(os.path.dirname(HERE), "include", "viekf_pixvel.h"))
     return out
 
 

@@ -292,6 +292,86 @@ class BatchVIEKF:
         self._keep = []
         return result, route.value
 
+    def update_pixel_vels(self, z, slot, gyro, R, gyro_var=0.0, active=None, order=0, result=None):
+        """M PIXEL_VEL (image velocity) updates per filter (viekf_batch_update_pixel_vels, include/viekf_pixvel.h).
+        z [B][M][2] px / s (pixel_flow), slot [B][M] (a slot may repeat; -1 = no entry), gyro [B][3] the raw gyro sample,
+        R (2,2), (B,2,2) or (B,M,2,2) indexed [row, col]; gyro_var the variance of one gyro axis; active [B][M] (0 / 1 / 2 as
+        update()) or None; order 0 = entry 0 first, 1 = entry M-1 first.  numpy arrays or contiguous CUDA tensors -- one call
+        takes one kind.
+        -> (result [B][M], route): route 1 = the fused launch, 0 = M launches of the single-entry kernel"""
+        self._keep = []
+        if len(slot.shape) != 2:
+            raise ValueError("slot must be [B][M]")
+        M = int(slot.shape[1])
+        ps, w = self._arg(slot, np.int32, (self.B, M), None)
+        pz, w = self._arg(z, np.float64, (self.B, M, 2), w)
+        pg, w = self._arg(gyro, np.float64, (self.B, 3), w)
+        Rc, r_mode = r_colmajor(R, self.B, M)
+        pR, w = self._arg(Rc, np.float64, tuple(Rc.shape), w)
+        if is_torch(Rc):
+            self._pixvels_R = Rc                               # (must outlive the queued work: kept until the next call)
+        pa, w = self._arg(active, np.uint8, (self.B, M), w)
+        if result is None:
+            if w == capi.DEVICE:
+                import torch
+                result = torch.empty((self.B, M), dtype=torch.int32, device=z.device)
+            else:
+                result = np.empty((self.B, M), dtype=np.int32)
+        pres, w = self._out(result, np.int32, (self.B, M), w)
+        route = C.c_int32(-1)
+        capi.check(capi.lib().viekf_batch_update_pixel_vels(self._h, M, ps, pz, pg, pR, r_mode, float(gyro_var), pa, int(order), pres,
+                                                            C.byref(route), w))
+        self._keep = []
+        return result, route.value
+
+    def pixel_vels_route(self, route):
+        """hold update_pixel_vels / FrameIntake.intake_pixel_vel of this batch to a route: -1 automatic, 0 the M launches, 1 fused"""
+        capi.check(capi.lib().viekf_batch_pixel_vels_route(self._h, int(route)))
+
+    def eval_pixel_vel(self, slot, gyro, jacobian=True):
+        """zhat = h_pixel_vel(x) [B][2] (px / s) at the current state for the feature in slot [B] and the raw gyro sample
+        gyro [B][3], and H [B][2][n] (None with jacobian=False): viekf_batch_eval_pixel_vel.  numpy arrays or contiguous CUDA
+        tensors; the filter is left untouched.  A slot outside [0, len): NaN."""
+        self._keep = []
+        ps, w = self._arg(slot, np.int32, (self.B,), None)
+        pg, w = self._arg(gyro, np.float64, (self.B, 3), w)
+        if w == capi.DEVICE:
+            import torch
+            zhat = torch.empty((self.B, 2), dtype=torch.float64, device=gyro.device)
+            H = torch.empty((self.B, 2, self.n), dtype=torch.float64, device=gyro.device) if jacobian else None
+        else:
+            zhat = np.empty((self.B, 2))
+            H = np.empty((self.B, 2, self.n)) if jacobian else None
+        pz, w = self._out(zhat, np.float64, (self.B, 2), w)
+        pH = None
+        if jacobian:
+            pH, w = self._out(H, np.float64, (self.B, 2, self.n), w)
+        capi.check(capi.lib().viekf_batch_eval_pixel_vel(self._h, ps, pg, pz, pH, w))
+        self._keep = []
+        return zhat, H
+
+    def pixel_flow(self, z_prev, ids_prev, z, ids, dt):
+        """the image velocity of a frame's features from the frame before, by id (viekf_pixel_flow): z_prev [B][Mp][2],
+        ids_prev [B][Mp], z [B][M][2], ids [B][M], dt [B] -> zdot [B][M][2], NaN where an id has no finite partner"""
+        self._keep = []
+        if len(ids.shape) != 2 or len(ids_prev.shape) != 2:
+            raise ValueError("ids and ids_prev must be [B][M]")
+        Mp, M = int(ids_prev.shape[1]), int(ids.shape[1])
+        pzp, w = self._arg(z_prev, np.float64, (self.B, Mp, 2), None)
+        pip, w = self._arg(ids_prev, np.int32, (self.B, Mp), w)
+        pz, w = self._arg(z, np.float64, (self.B, M, 2), w)
+        pi, w = self._arg(ids, np.int32, (self.B, M), w)
+        pdt, w = self._arg(dt, np.float64, (self.B,), w)
+        if w == capi.DEVICE:
+            import torch
+            zdot = torch.empty((self.B, M, 2), dtype=torch.float64, device=z.device)
+        else:
+            zdot = np.empty((self.B, M, 2))
+        po, w = self._out(zdot, np.float64, (self.B, M, 2), w)
+        capi.check(capi.lib().viekf_pixel_flow(self._h, Mp, pzp, pip, M, pz, pi, pdt, po, w))
+        self._keep = []
+        return zdot
+
     def keep_features(self, keep):
         """drop the features with keep[b, f] == 0 and compact (reference vi_ekf_feat.cpp:50-117) -> new len [B]"""
         self._keep = []

@@ -46,6 +46,12 @@ BODY_MAX_M = 8
 DEPTH_SYMBOLS = ["viekf_batch_update_depths", "viekf_depths_lds_bytes", "viekf_frame_intake_depth"]
 DEPTHS_MAX_M = 256
 
+# what include/viekf_pixvel.h declares (the PIXEL_VEL measurement: BatchVIEKF.update_pixel_vels / eval_pixel_vel,
+# vi_ekf_amd.pixel_flow, FrameIntake.intake_pixel_vel)
+PIXVEL_SYMBOLS = ["viekf_batch_update_pixel_vels", "viekf_pixvel_lds_bytes", "viekf_pixvels_lds_bytes", "viekf_batch_pixel_vels_route", "viekf_batch_eval_pixel_vel", "viekf_pixel_flow",
+                  "viekf_frame_intake_pixel_vel"]
+PIXVELS_MAX_M = 256
+
 
 class Params(C.Structure):
     """struct viekf_params (include/viekf.h) == the keys VIEKF::load reads (reference vi_ekf.cpp:114-131)."""
@@ -176,6 +182,17 @@ def lib():
         L.viekf_depths_lds_bytes.argtypes = [C.c_int32, C.c_int32]
         L.viekf_depths_lds_bytes.restype = C.c_int64
         L.viekf_frame_intake_depth.argtypes = [_vp, C.c_int32, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, _vp, _vp, C.c_int]
+        L.viekf_batch_update_pixel_vels.argtypes = [_vp, C.c_int32, _vp, _vp, _vp, _vp, C.c_int32, C.c_double, _vp, C.c_int32, _vp,
+                                                    C.POINTER(C.c_int32), C.c_int]
+        L.viekf_pixvel_lds_bytes.argtypes = [C.c_int32]
+        L.viekf_pixvels_lds_bytes.argtypes = [C.c_int32, C.c_int32]
+        L.viekf_pixvels_lds_bytes.restype = C.c_int64
+        L.viekf_batch_pixel_vels_route.argtypes = [_vp, C.c_int32]
+        L.viekf_pixvel_lds_bytes.restype = C.c_int64
+        L.viekf_batch_eval_pixel_vel.argtypes = [_vp, _vp, _vp, _vp, _vp, C.c_int]
+        L.viekf_pixel_flow.argtypes = [_vp, C.c_int32, _vp, _vp, C.c_int32, _vp, _vp, _vp, _vp, C.c_int]
+        L.viekf_frame_intake_pixel_vel.argtypes = [_vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_double, C.c_int32, _vp, _vp,
+                                                   C.c_int]
         _lib = L
     return _lib
 

@@ -55,6 +55,7 @@ struct viekf_batch {
                                        // the fused kernel itself when it stores a filter into another slot
   int* d_zero = nullptr;               // [B] zeros (gather / scatter between the ring and the batch's own buffers)
   double* d_body_z = nullptr;          // [VIEKF_BODY_MAX_M][B][4] viekf_batch_update_body's M-launch route: z repacked per entry (first use)
+  int pixvel_route = -1;               // viekf_batch_pixel_vels_route: -1 automatic, 0 always the M launches, 1 fused where it fits
   double* d_depth_m = nullptr;         // [4 B + 8] viekf_batch_update_depths' M-launch route: one entry's z, R, slot, result and active per filter (first use)
   // async host inputs (viekf_batch_set_async): pinned staging ring the arguments are copied into at call time
   bool async_host = false;

@@ -1013,6 +1013,7 @@ int viekf_batch_step_n(viekf_batch* b, int32_t K, const double* u, const double*
 #include "viekf_capi_diag.hpp"
 #include "viekf_capi_frame.hpp"
 #include "viekf_capi_depth.hpp"
+#include "viekf_capi_pixvel.hpp"
 #include "viekf_capi_node.hpp"
 #include "viekf_capi_map.hpp"
 #include "viekf_capi_rec.hpp"

@@ -15,6 +15,7 @@
 #include "viekf_kernels_generic.hpp"
 #include "viekf_kernels_hooks.hpp"
 #include "viekf_kernels_lifecycle.hpp"
+#include "viekf_kernels_pixvel.hpp"
 #include "viekf_kernels_stream.hpp"
 #include "viekf_kernels_util.hpp"
 #include "viekf_kernels_wide.hpp"

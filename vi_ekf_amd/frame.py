@@ -128,3 +128,32 @@ class FrameIntake(Companion):
         capi.check(self._L.viekf_frame_intake_depth(h, M, pi, pd, pf, pR, r_mode, 1 if use_depth else 0, pa, pres, w))
         self._done(dev, True)
         return result
+
+    def intake_pixel_vel(self, out_or_result, ids, zdot, gyro, R, gyro_var=0.0, use_pixel_vel=True, active=None):
+        """the frame's PIXEL_VEL measurements, behind intake() (and intake_depth()) of the same frame
+        (viekf_frame_intake_pixel_vel, include/viekf_pixvel.h): out_or_result = what intake() returned, or its "result" [B][M];
+        ids [B][M] as given to intake(); zdot [B][M][2] the flow (pixel_flow), NaN where there is none; gyro [B][3] the raw gyro
+        sample; R (2,2), (B,2,2) or (B,M,2,2) indexed [row, col]; use_pixel_vel False = inactive measurements (fix_depth only);
+        active [B] uint8 or None -> result [B][M], where the inputs live"""
+        g = self.batch
+        h = self._handle()
+        g._keep = []
+        B = g.B
+        fres = out_or_result["result"] if isinstance(out_or_result, dict) else out_or_result
+        if len(ids.shape) != 2:
+            raise ValueError("ids must be [B][M]")
+        M = int(ids.shape[1])
+        pi, w = g._arg(ids, np.int32, (B, M), None)
+        pd, w = g._arg(zdot, np.float64, (B, M, 2), w)
+        pf, w = g._arg(fres, np.int32, (B, M), w)
+        pg, w = g._arg(gyro, np.float64, (B, 3), w)
+        Rc, r_mode = r_colmajor(R, B, M)
+        pR, w = g._arg(Rc, np.float64, tuple(Rc.shape), w)
+        pa, w = g._arg(active, np.uint8, (B,), w)
+        dev = w == capi.DEVICE
+        result, pres = self._empty((B, M), np.int32, dev)
+        self._ready(dev, True)
+        capi.check(self._L.viekf_frame_intake_pixel_vel(h, M, pi, pd, pf, pg, pR, r_mode, float(gyro_var), 1 if use_pixel_vel else 0,
+                                                        pa, pres, w))
+        self._done(dev, True)
+        return result
