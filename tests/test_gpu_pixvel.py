@@ -4,7 +4,7 @@ P with assert_close of tests/test_gpu_parity.py, and P == P^T is checked.  The c
 states are in tests/pixvel_cases.py; tests/test_pixvel_ref_cpu.py checks the model itself (finite differences, the oracle's
 dynamics, the simulator's kinematics) and that the cases reach what they are for.
 
-Sizes: N = 1, 3, 12 (n = 19, 25, 52), 2 with M = 70, B = 5 with the ragged fill [N, N - 3, 1, 0, N - 1] clipped at 0."""
+Sizes: N = 1, 3, 12 (n = 19, 25, 52), 16, 17, 44 (n = 64, 67, 148: past a 64-row block), 2 with M = 70, B = 5 with the ragged fill [N, N - 3, 1, 0, N - 1] clipped at 0."""
 import ctypes as C
 
 import numpy as np
@@ -101,6 +101,16 @@ def test_eval_pixel_vel(N, drag):
 def test_every_slot_once(N, variant):
     """M = N entries, per-filter shuffled slots (slots >= len: INVALID; a -1: SKIPPED); partial update on and off, the three R
     modes with a different R per entry, both orders, gyro_var 0 and > 0, drag on and off"""
+    c = pc.case("once", N, variant)
+    g, res, x, P = run_case(c)
+    assert not g.get_status().any()
+
+
+@pytest.mark.parametrize("N,variant", [(N, vv) for N in (16, 17, 44) for vv in (0, 3)])
+def test_every_slot_once_past_a_row_block(N, variant):
+    """nact = 64, 67, 148 in the full filter: one 64-row block of the trailing pass (and of route 0's column walk) exactly, one
+    row into the second, a partly filled third -- the partly valid last block and the j <= i mask across blocks; partial update
+    on with order 0, off with order 1"""
     c = pc.case("once", N, variant)
     g, res, x, P = run_case(c)
     assert not g.get_status().any()

@@ -24,9 +24,9 @@ int body_lds_limit(int device, size_t* bytes) {
 extern "C" {
 
 int64_t viekf_body_lds_bytes(int32_t num_features, int32_t M) {
-  if (num_features < 0 || num_features > 4096 || M < 1 || M > VIEKF_BODY_MAX_M) return 0;
-  const int nx = 17 + 5 * num_features;
-  return (int64_t)BodyLds((nx + 1) & ~1, 16 + 3 * num_features, M).bytes();
+  int nxs = 0, n = 0;
+  if (!lds_dims(num_features, &nxs, &n) || M < 1 || M > VIEKF_BODY_MAX_M) return 0;
+  return (int64_t)BodyLds(nxs, n, M).bytes();
 }
 
 int viekf_body_lds_limit(int32_t device, int64_t* bytes) {

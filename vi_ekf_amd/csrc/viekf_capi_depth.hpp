@@ -27,7 +27,8 @@ int depths_launch(viekf_batch* b, int type, int M, const int32_t* d_slot, const 
   if (int rc = require_P(b, fused ? PForm::Lower : PForm::Full)) return rc;
   StreamArgs a = make_args(b);
   if (fused) {
-    const long rsb = r_mode == 1 ? 1L : (r_mode == 2 ? (long)M : 0L), rsm = r_mode == 2 ? 1L : 0L;
+    long rsb = 0, rsm = 0;
+    r_strides(r_mode, M, &rsb, &rsm, 1);
     static size_t have[64] = {};
     if (int rc = raise_dyn_lds({&k_update_depths<kThreads, MT_DEPTH>, &k_update_depths<kThreads, MT_INV_DEPTH>}, L.bytes(),
                                have[b->device & 63]))
@@ -68,9 +69,9 @@ int depths_launch(viekf_batch* b, int type, int M, const int32_t* d_slot, const 
 extern "C" {
 
 int64_t viekf_depths_lds_bytes(int32_t num_features, int32_t M) {
-  if (num_features < 0 || num_features > 4096 || M < 1 || M > VIEKF_DEPTHS_MAX_M) return 0;
-  const int nx = 17 + 5 * num_features;
-  return (int64_t)DepthLds((nx + 1) & ~1, 16 + 3 * num_features, M).bytes();
+  int nxs = 0, n = 0;
+  if (!lds_dims(num_features, &nxs, &n) || M < 1 || M > VIEKF_DEPTHS_MAX_M) return 0;
+  return (int64_t)DepthLds(nxs, n, M).bytes();
 }
 
 int viekf_batch_update_depths(viekf_batch* b, int32_t type, int32_t M, const int32_t* slot, const double* z, const double* R,
@@ -98,21 +99,16 @@ int viekf_batch_update_depths(viekf_batch* b, int32_t type, int32_t M, const int
   return st.finish();
 }
 
-// k_frame_depth_plan (id -> slot on the intake's table, which entries measure) -> viekf_batch_update_depths' launches, all on
-// the batch's stream; the slots and the per-entry `active` sit in the intake's own per-frame rows, free again after the intake.
+// intake_step_plan -> viekf_batch_update_depths' launches, all on the batch's stream.
 int viekf_frame_intake_depth(viekf_frame* f, int32_t M, const int32_t* ids, const double* depth, const int32_t* feat_result,
                              const double* R, int32_t r_mode, int32_t use_depth, const uint8_t* active, int32_t* result,
                              viekf_mem where) {
-  if (int rc = check_frame(f)) return rc;
+  static const IntakeStepMsgs msg = {
+      "need 1 <= M <= VIEKF_DEPTHS_MAX_M entries per frame", "ids, depth, feat_result and R must not be null",
+      "viekf_frame_intake_depth under a participation mask (viekf_batch_set_active(NULL) first; the call takes its own `active`)"};
+  if (int rc = intake_step_begin(f, M, VIEKF_DEPTHS_MAX_M, ids && depth && feat_result && R, r_mode, nullptr, where, msg))
+    return rc;
   viekf_batch* b = f->b;
-  if (M < 1 || M > VIEKF_DEPTHS_MAX_M) return fail(VIEKF_ERR_INVALID, "need 1 <= M <= VIEKF_DEPTHS_MAX_M entries per frame");
-  if (!ids || !depth || !feat_result || !R) return fail(VIEKF_ERR_INVALID, "ids, depth, feat_result and R must not be null");
-  if (r_mode < 0 || r_mode > 2) return fail(VIEKF_ERR_INVALID, "r_mode must be 0, 1 or 2");
-  if (int rc = check_where(where)) return rc;
-  if (b->active_on)
-    return fail(VIEKF_ERR_INVALID, "viekf_frame_intake_depth under a participation mask (viekf_batch_set_active(NULL) first; the call takes its own `active`)");
-  HIP_TRY(hipSetDevice(b->device));
-  if (int rc = frame_reserve(f, M)) return rc;
   const size_t B = (size_t)b->B, BM = B * (size_t)M;
   const int32_t *d_ids = nullptr, *d_fr = nullptr;
   const double *d_depth = nullptr, *d_R = nullptr;
@@ -122,12 +118,9 @@ int viekf_frame_intake_depth(viekf_frame* f, int32_t M, const int32_t* ids, cons
   if (int rc = st.begin(in(ids, BM, &d_ids), in(depth, BM, &d_depth), in(feat_result, BM, &d_fr), in(R, r_count(b, M, r_mode, 1), &d_R),
                         in(active, B, &d_act), out(result, BM, &d_res)))
     return rc;
-  const FrameTabs& t = f->t;
-  unsigned char* act_d = reinterpret_cast<unsigned char*>(t.code);
-  hipLaunchKernelGGL(k_frame_depth_plan, dim3(b->B), dim3(64), 0, b->stream, b->B, b->N, M, b->d_len, t.tab, t.tlen, d_ids, d_depth, d_fr,
-                     d_act, use_depth ? 1 : 0, t.slot_u, act_d);
-  HIP_TRY(hipGetLastError());
-  if (int rc = depths_launch(b, VIEKF_DEPTH, M, t.slot_u, d_depth, d_R, r_mode, act_d, 1, d_res, nullptr)) return rc;
+  unsigned char* act_d = nullptr;
+  if (int rc = intake_step_plan<1>(f, M, d_ids, d_depth, d_fr, d_act, use_depth, &act_d)) return rc;
+  if (int rc = depths_launch(b, VIEKF_DEPTH, M, f->t.slot_u, d_depth, d_R, r_mode, act_d, 1, d_res, nullptr)) return rc;
   return st.finish();
 }
 

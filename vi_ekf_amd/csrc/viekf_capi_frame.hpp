@@ -3,6 +3,8 @@
 // the batch's own kernels (keep, keyframe reset, init, the FEAT update) through viekf_dispatch.hpp, which is why this is part
 // of the one translation unit: included by viekf_capi.hip ONLY.
 #pragma once
+#include <cmath>
+
 #include "../../include/viekf_frame.h"
 #include "viekf_dispatch.hpp"
 #include "viekf_kernels_frame.hpp"
@@ -56,6 +58,43 @@ int frame_reserve(viekf_frame* f, int M) {
   if (int rc2 = own.free(&t.kf)) return rc2;
   t.kf = kf; t.kfcap = cap;
   f->mcap = cap;
+  return VIEKF_OK;
+}
+
+int check_gyro_var(double gyro_var) {
+  if (!(gyro_var >= 0.0) || !std::isfinite(gyro_var)) return fail(VIEKF_ERR_INVALID, "gyro_var must be finite and >= 0");
+  return VIEKF_OK;
+}
+
+// What the intake's measurement steps (viekf_frame_intake_depth, viekf_frame_intake_pixel_vel) check alike, in their order and
+// under the entry point's own messages, then the rows for M entries.  have_all: none of the step's arrays is null; gyro_var:
+// NULL where the step has none.
+struct IntakeStepMsgs { const char *m_range, *null_arg, *mask; };
+int intake_step_begin(viekf_frame* f, int M, int max_M, bool have_all, int r_mode, const double* gyro_var, viekf_mem where,
+                      const IntakeStepMsgs& msg) {
+  if (int rc = check_frame(f)) return rc;
+  if (M < 1 || M > max_M) return fail(VIEKF_ERR_INVALID, msg.m_range);
+  if (!have_all) return fail(VIEKF_ERR_INVALID, msg.null_arg);
+  if (r_mode < 0 || r_mode > 2) return fail(VIEKF_ERR_INVALID, "r_mode must be 0, 1 or 2");
+  if (gyro_var)
+    if (int rc = check_gyro_var(*gyro_var)) return rc;
+  if (int rc = check_where(where)) return rc;
+  if (f->b->active_on) return fail(VIEKF_ERR_INVALID, msg.mask);
+  HIP_TRY(hipSetDevice(f->b->device));
+  return frame_reserve(f, M);
+}
+
+// k_frame_slot_plan (id -> slot on the intake's table, which entries measure) on the batch's stream: the slots go to the
+// intake's slot_u, the per-entry `active` (*act_d) to its code row -- per-frame rows, free again after the intake.
+template <int ZD>
+int intake_step_plan(viekf_frame* f, int M, const int32_t* d_ids, const double* d_val, const int32_t* d_fr, const uint8_t* d_act,
+                     int use, unsigned char** act_d) {
+  viekf_batch* b = f->b;
+  const FrameTabs& t = f->t;
+  *act_d = reinterpret_cast<unsigned char*>(t.code);
+  hipLaunchKernelGGL(k_frame_slot_plan<ZD>, dim3(b->B), dim3(64), 0, b->stream, b->B, b->N, M, b->d_len, t.tab, t.tlen, d_ids, d_val, d_fr,
+                     d_act, use ? 1 : 0, t.slot_u, *act_d);
+  HIP_TRY(hipGetLastError());
   return VIEKF_OK;
 }
 

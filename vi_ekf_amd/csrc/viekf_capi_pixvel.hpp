@@ -55,19 +55,14 @@ int pixvels_launch(viekf_batch* b, int M, const int32_t* d_slot, const double* d
   return VIEKF_OK;
 }
 
-int check_gyro_var(double gyro_var) {
-  if (!(gyro_var >= 0.0) || !std::isfinite(gyro_var)) return fail(VIEKF_ERR_INVALID, "gyro_var must be finite and >= 0");
-  return VIEKF_OK;
-}
-
 }  // namespace
 
 extern "C" {
 
 int64_t viekf_pixvels_lds_bytes(int32_t num_features, int32_t M) {
-  if (num_features < 0 || num_features > 4096 || M < 1 || M > VIEKF_PIXVELS_MAX_M) return 0;
-  const int nx = 17 + 5 * num_features;
-  return (int64_t)PixvelsLds((nx + 1) & ~1, 16 + 3 * num_features, num_features, M).bytes();
+  int nxs = 0, n = 0;
+  if (!lds_dims(num_features, &nxs, &n) || M < 1 || M > VIEKF_PIXVELS_MAX_M) return 0;
+  return (int64_t)PixvelsLds(nxs, n, num_features, M).bytes();
 }
 
 int viekf_batch_pixel_vels_route(viekf_batch* b, int32_t route) {
@@ -78,9 +73,8 @@ int viekf_batch_pixel_vels_route(viekf_batch* b, int32_t route) {
 }
 
 int64_t viekf_pixvel_lds_bytes(int32_t num_features) {
-  if (num_features < 0 || num_features > 4096) return 0;
-  const int nx = 17 + 5 * num_features;
-  return (int64_t)PixvelLds((nx + 1) & ~1, 16 + 3 * num_features).bytes();
+  int nxs = 0, n = 0;
+  return lds_dims(num_features, &nxs, &n) ? (int64_t)PixvelLds(nxs, n).bytes() : 0;
 }
 
 int viekf_batch_update_pixel_vels(viekf_batch* b, int32_t M, const int32_t* slot, const double* z, const double* gyro, const double* R,
@@ -145,22 +139,16 @@ int viekf_pixel_flow(viekf_batch* b, int32_t M_prev, const double* z_prev, const
   return st.finish();
 }
 
-// k_frame_pixvel_plan (id -> slot on the intake's table, which entries measure) -> the update's launches, all on the batch's
-// stream; the slots and the per-entry `active` sit in the intake's own per-frame rows, free again after the intake.
+// intake_step_plan -> the update's launches, all on the batch's stream.
 int viekf_frame_intake_pixel_vel(viekf_frame* f, int32_t M, const int32_t* ids, const double* zdot, const int32_t* feat_result,
                                  const double* gyro, const double* R, int32_t r_mode, double gyro_var, int32_t use_pixel_vel,
                                  const uint8_t* active, int32_t* result, viekf_mem where) {
-  if (int rc = check_frame(f)) return rc;
+  static const IntakeStepMsgs msg = {
+      "need 1 <= M <= VIEKF_PIXVELS_MAX_M entries per frame", "ids, zdot, feat_result, gyro and R must not be null",
+      "viekf_frame_intake_pixel_vel under a participation mask (viekf_batch_set_active(NULL) first; the call takes its own `active`)"};
+  if (int rc = intake_step_begin(f, M, VIEKF_PIXVELS_MAX_M, ids && zdot && feat_result && gyro && R, r_mode, &gyro_var, where, msg))
+    return rc;
   viekf_batch* b = f->b;
-  if (M < 1 || M > VIEKF_PIXVELS_MAX_M) return fail(VIEKF_ERR_INVALID, "need 1 <= M <= VIEKF_PIXVELS_MAX_M entries per frame");
-  if (!ids || !zdot || !feat_result || !gyro || !R) return fail(VIEKF_ERR_INVALID, "ids, zdot, feat_result, gyro and R must not be null");
-  if (r_mode < 0 || r_mode > 2) return fail(VIEKF_ERR_INVALID, "r_mode must be 0, 1 or 2");
-  if (int rc = check_gyro_var(gyro_var)) return rc;
-  if (int rc = check_where(where)) return rc;
-  if (b->active_on)
-    return fail(VIEKF_ERR_INVALID, "viekf_frame_intake_pixel_vel under a participation mask (viekf_batch_set_active(NULL) first; the call takes its own `active`)");
-  HIP_TRY(hipSetDevice(b->device));
-  if (int rc = frame_reserve(f, M)) return rc;
   const size_t B = (size_t)b->B, BM = B * (size_t)M;
   const int32_t *d_ids = nullptr, *d_fr = nullptr;
   const double *d_zd = nullptr, *d_g = nullptr, *d_R = nullptr;
@@ -170,12 +158,9 @@ int viekf_frame_intake_pixel_vel(viekf_frame* f, int32_t M, const int32_t* ids, 
   if (int rc = st.begin(in(ids, BM, &d_ids), in(zdot, 2 * BM, &d_zd), in(feat_result, BM, &d_fr), in(gyro, 3 * B, &d_g),
                         in(R, r_count(b, M, r_mode), &d_R), in(active, B, &d_act), out(result, BM, &d_res)))
     return rc;
-  const FrameTabs& t = f->t;
-  unsigned char* act_d = reinterpret_cast<unsigned char*>(t.code);
-  hipLaunchKernelGGL(k_frame_pixvel_plan, dim3(b->B), dim3(64), 0, b->stream, b->B, b->N, M, b->d_len, t.tab, t.tlen, d_ids, d_zd, d_fr,
-                     d_act, use_pixel_vel ? 1 : 0, t.slot_u, act_d);
-  HIP_TRY(hipGetLastError());
-  if (int rc = pixvels_launch(b, M, t.slot_u, d_zd, d_g, d_R, r_mode, gyro_var, act_d, 1, d_res, nullptr)) return rc;
+  unsigned char* act_d = nullptr;
+  if (int rc = intake_step_plan<2>(f, M, d_ids, d_zd, d_fr, d_act, use_pixel_vel, &act_d)) return rc;
+  if (int rc = pixvels_launch(b, M, f->t.slot_u, d_zd, d_g, d_R, r_mode, gyro_var, act_d, 1, d_res, nullptr)) return rc;
   return st.finish();
 }
 

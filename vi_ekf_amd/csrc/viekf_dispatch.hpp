@@ -51,9 +51,15 @@ int raise_dyn_lds(std::initializer_list<Kernel*> kernels, size_t bytes, size_t& 
 size_t r_count(const viekf_batch* b, int M, int r_mode, size_t rr = 4) {
   return r_mode == 0 ? rr : (r_mode == 1 ? rr * (size_t)b->B : rr * (size_t)b->B * M);
 }
-void r_strides(int r_mode, int M, long* rsb, long* rsm) {
-  *rsb = r_mode == 1 ? 4 : (r_mode == 2 ? 4L * M : 0);
-  *rsm = r_mode == 2 ? 4 : 0;
+void r_strides(int r_mode, int M, long* rsb, long* rsm, long rr = 4) {
+  *rsb = r_mode == 1 ? rr : (r_mode == 2 ? rr * M : 0);
+  *rsm = r_mode == 2 ? rr : 0;
+}
+// (nxs, n) of a batch with num_features slots, for the *_lds_bytes entry points; false outside what they answer for
+bool lds_dims(int num_features, int* nxs, int* n) {
+  *nxs = (17 + 5 * num_features + 1) & ~1;
+  *n = 16 + 3 * num_features;
+  return num_features >= 0 && num_features <= 4096;
 }
 
 // A grouped update (k_update_feat_blocked) keeps only the lower triangle of P current; the matrix-core propagate reads only

@@ -5,6 +5,7 @@
 #include "viekf_body_lds.hpp"
 #include "viekf_kernel_args.hpp"
 #include "viekf_meas_models.hpp"
+#include "viekf_onepass.hpp"
 
 namespace viekf {
 
@@ -48,8 +49,7 @@ __device__ __forceinline__ void body_trailing(double* __restrict__ P, int ld, in
       for (int u = 0; u < UN; u++) {
         const int j = j0 + u * NW;
         if (!ok[u]) continue;
-        const double lj = lam[j];
-        const double L = partial ? (lj + li - li * lj) : 1.0;
+        const double L = partial ? partial_L(li, lam[j]) : 1.0;
         const double* Wj = Wall + WL * j;
         double v = p[u];
 #pragma unroll
@@ -94,12 +94,6 @@ __device__ __attribute__((noinline)) unsigned body_entry(const StreamArgs& a, in
   const int nxa = xZ + 5 * len;
   const bool partial = prm.use_partial_update != 0;
   unsigned st = 0;
-  auto fix_depth_lds = [&](int f, unsigned& flag) {   // fix_depth_one with P(rho, rho) in D
-    const int xR = xZ + 5 * f + 4;
-    double rho = xs[xR];
-    fix_depth_rule(rho, 1.0 / (2.0 * prm.min_depth), flag, [&](double e2) { D[f] += e2; }, [&] { D[f] = prm.P0_feat[2]; });
-    xs[xR] = rho;
-  };
   const int type = code & 15, rdim = (code >> 4) & 3, zdim = (code >> 6) + 1;
   const int act = active_all ? active_all[(long)m * a.B + b] : 1;
   int* res_out = result_all ? &result_all[(long)m * a.B + b] : nullptr;
@@ -112,7 +106,7 @@ __device__ __attribute__((noinline)) unsigned body_entry(const StreamArgs& a, in
   }
   __syncthreads();   // what the load or the entry before wrote (xs, C, D); sm is free again
   if (act == 0) {    // :230 -- an inactive measurement only runs fix_depth
-    for (int f = tid; f < len; f += T) fix_depth_lds(f, st);
+    for (int f = tid; f < len; f += T) fix_depth_diag(xs, D, f, prm, st);
     if (res_out && tid == 0) *res_out = 0;
     st |= kBodyDirty;
     return st;
@@ -197,8 +191,7 @@ __device__ __attribute__((noinline)) unsigned body_entry(const StreamArgs& a, in
       const int dr = d + 2;
       double t = 0.0;
       for (int q = 0; q < rdim; q++) t += K[3 * dr + q] * W[WL * dr + q];
-      const double lr = lam[dr];
-      D[f] -= (partial ? (lr + lr - lr * lr) : 1.0) * t;
+      D[f] -= (partial ? partial_L(lam[dr], lam[dr]) : 1.0) * t;
     }
     // the panel: the next entry's W comes from here
     for (int i = tid; i < nact; i += T) {
@@ -208,15 +201,13 @@ __device__ __attribute__((noinline)) unsigned body_entry(const StreamArgs& a, in
         const int hi = max(i, c), lo = min(i, c);   // (exactly symmetric, as k_update_generic)
         double t = 0.0;
         for (int q = 0; q < rdim; q++) t += K[3 * hi + q] * W[WL * lo + q];
-        const double lj = lam[c];
-        const double L = partial ? (lj + li - li * lj) : 1.0;
-        Cp[CL * i + c] -= L * t;
+        Cp[CL * i + c] -= (partial ? partial_L(li, lam[c]) : 1.0) * t;
       }
     }
     st |= kBodyApplied;   // K and W of this entry stay for the trailing pass
   }
   __syncthreads();
-  for (int f = tid; f < len; f += T) fix_depth_lds(f, st);
+  for (int f = tid; f < len; f += T) fix_depth_diag(xs, D, f, prm, st);
   __syncthreads();
   for (int i = tid; i < nxa; i += T) {   // the scan k_update_generic makes when it writes x back
     const double v = xs[i];

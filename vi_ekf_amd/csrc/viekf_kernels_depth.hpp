@@ -1,68 +1,14 @@
 // viekf_kernels_depth.hpp -- the DEPTH (or INV_DEPTH) updates of one camera frame (what color_image_callback queues behind every
-// FEAT it queued, vi_ekf_ros.cpp:287-305, handed to VIEKF::update) in ONE pass over P, the gather / scatter kernels of the
-// M-launch route and the id -> slot lookup of the intake's depth step.  Defines kernels: included from viekf_dispatch.hpp only.
+// FEAT it queued, vi_ekf_ros.cpp:287-305, handed to VIEKF::update) in ONE pass over P and the gather / scatter kernels of the
+// M-launch route.  (The id -> slot lookup of the intake's depth step: k_frame_slot_plan, viekf_kernels_frame.hpp.)
+// Defines kernels: included from viekf_dispatch.hpp only.
 #pragma once
 #include "viekf_depth_lds.hpp"
 #include "viekf_kernel_args.hpp"
 #include "viekf_meas_models.hpp"
+#include "viekf_onepass.hpp"
 
 namespace viekf {
-
-// One applied entry's downdate of one element:  v -= L (K[hi] W[lo]),  K[hi] = W[hi] S^-1 -- operation by operation what
-// k_update_generic does to P(i, j) with hi = max(i, j), lo = min(i, j) (its K, its t, its P -= L t).
-__device__ __forceinline__ double depth_downdate(double v, double L, double whi, double wlo, double si) {
-  double k = 0.0;
-  k += whi * si;
-  double t = 0.0;
-  t += k * wlo;
-  return v - L * t;
-}
-
-// The trailing pass of k_update_depths for napp applied entries: the lower triangle of the active block, rho diagonals excepted
-// (they are stored from D).  A lane keeps ROW i (64 consecutive rows per wave: a column's segment is 512 contiguous bytes); a
-// wave takes UN adjacent columns at a time, loads before arithmetic; per entry a lane reads its own W (one conflict-free read),
-// S^-1 and the UN column values (broadcasts).  The entries run innermost, in order, on the values held in registers.
-template <int T>
-__device__ __forceinline__ void depth_trailing(double* __restrict__ P, int ld, int nact, int nW, int napp, bool partial,
-                                               const double* Wall, const double* Sinv, const double* lam) {
-  constexpr int NW = T / 64;   // waves
-  constexpr int UN = 8;        // columns a wave has in flight
-  const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  for (int r0 = 0; r0 < nact; r0 += 64) {
-    const int i = r0 + lane;
-    const bool valid = i < nact;
-    const int ir = valid ? i : 0;
-    const double li = lam[ir];
-    const bool isrho = i >= dxZ && (i - dxZ) % 3 == 2;
-    const int jend = min(r0 + 63, nact - 1);
-    for (int j0 = wid * UN; j0 <= jend; j0 += NW * UN) {
-      double p[UN], L[UN];
-      bool ok[UN];
-#pragma unroll
-      for (int u = 0; u < UN; u++) {
-        const int j = j0 + u;
-        ok[u] = valid && j <= i && !(i == j && isrho);   // (j <= i < nact)
-        p[u] = 0.0;
-        if (ok[u]) p[u] = P[i + (long)j * ld];
-      }
-#pragma unroll
-      for (int u = 0; u < UN; u++) {
-        const double lj = lam[min(j0 + u, nact - 1)];
-        L[u] = partial ? (lj + li - li * lj) : 1.0;
-      }
-#pragma unroll 2
-      for (int k = 0; k < napp; k++) {
-        const double* Wk = Wall + (long)k * nW;
-        const double wi = Wk[ir], si = Sinv[k];
-#pragma unroll
-        for (int u = 0; u < UN; u++) p[u] = depth_downdate(p[u], L[u], wi, Wk[min(j0 + u, nact - 1)], si);
-      }
-#pragma unroll
-      for (int u = 0; u < UN; u++)
-        if (ok[u]) P[i + (long)(j0 + u) * ld] = p[u];
-    }
-  }
-}
 
 // ------------------------------------------------------------------------------------------------
 // M DEPTH (TYPE = MT_DEPTH) or INV_DEPTH measurements per filter, applied in order, with the arithmetic of M launches of
@@ -71,10 +17,7 @@ __device__ __forceinline__ void depth_trailing(double* __restrict__ P, int ld, i
 // h_depth / h_inv_depth have ONE non-zero element of H, at column c = 16 + 3 slot + 2: W = P H^T is that column of the
 // current P times a scalar, S and K = W S^-1 follow from it.  The chain runs left-looking: the column an entry needs is the
 // start P's column minus the downdates of the entries applied before it, which their W and S^-1 in LDS give
-// (depth_downdate).  fix_depth edits P(rho, rho), which later entries only subtract from: those diagonals ride along in D,
-// and the diagonal element of a column comes from D.  Every element of the lower triangle gets the downdates of the applied
-// entries, in entry order, in the trailing pass: loaded once, stored once.  Nothing above the diagonal, at or past row /
-// column nact, or in the pad rows is read or written.
+// (onepass_rebuild<1>).  The rho diagonals in D, the trailing pass and what is never touched: viekf_onepass.hpp.
 //
 // One workgroup per filter; a.si(b) is followed.  The rules of an entry, in k_update_generic's order: include/viekf_depth.h.
 // ------------------------------------------------------------------------------------------------
@@ -104,16 +47,13 @@ __global__ __launch_bounds__(T) void k_update_depths(StreamArgs a, int M, int or
   double* P = a.P + a.si(b) * n * ld;
   const int len = a.len[b];
   const int nact = 16 + 3 * len;
-  const int nxa = xZ + 5 * len;
   const bool partial = prm.use_partial_update != 0;
   const long row = (long)b * M;
   auto entry_of = [&](int e) { return order ? M - 1 - e : e; };
 
   // ---- load: x, lambda, the rho diagonals, and for every entry the column of the start P its slot names (lower triangle only:
   //      row i of column c, or its mirror image) -- all of the chain's global loads, issued together ----
-  for (int i = tid; i < nxa; i += T) xs[i] = xg[i];
-  for (int i = tid; i < n; i += T) lam[i] = a.lambda[i];
-  for (int f = tid; f < len; f += T) { const long dR = dxZ + 3 * f + 2; D[f] = P[dR + dR * ld]; }
+  onepass_load<T>(a, xg, P, len, xs, lam, D);
   for (int i = tid; i < nact; i += T) {
     constexpr int UL = 8;   // columns a thread has in flight (the chain cannot start before the last of them is in)
     for (int e0 = 0; e0 < M; e0 += UL) {
@@ -134,13 +74,6 @@ __global__ __launch_bounds__(T) void k_update_depths(StreamArgs a, int M, int or
     }
   }
 
-  auto fix_depth_lds = [&](int f, unsigned& flag) {   // fix_depth_one with P(rho, rho) in D
-    const int xR = xZ + 5 * f + 4;
-    double rho = xs[xR];
-    fix_depth_rule(rho, 1.0 / (2.0 * prm.min_depth), flag, [&](double e2) { D[f] += e2; }, [&] { D[f] = prm.P0_feat[2]; });
-    xs[xR] = rho;
-  };
-
   // ---- chain ----
   unsigned flag = 0;    // (per thread; ORed into the filter's word at the end)
   int napp = 0;         // entries applied so far: the row of W / Si the next one writes
@@ -156,7 +89,7 @@ __global__ __launch_bounds__(T) void k_update_depths(StreamArgs a, int M, int or
     if (z != z) { if (res_out) *res_out = 2; continue; }   // MEAS_NAN
     __syncthreads();   // what the load or the entry before wrote (xs, D, W, Si)
     if (act == 0) {    // :230 -- an inactive measurement only runs fix_depth
-      for (int f = tid; f < len; f += T) fix_depth_lds(f, flag);
+      for (int f = tid; f < len; f += T) fix_depth_diag(xs, D, f, prm, flag);
       if (res_out) *res_out = 0;
       dirty = true;
       continue;
@@ -174,9 +107,8 @@ __global__ __launch_bounds__(T) void k_update_depths(StreamArgs a, int M, int or
       double v = Wall[(long)e * nW + i];
       const int hi = max(i, c), lo = min(i, c);
       const double li = lam[i];
-      const double L = partial ? (lc + li - li * lc) : 1.0;
-#pragma unroll 4   // (the reads of four entries in flight; the downdates stay in entry order)
-      for (int k = 0; k < napp; k++) v = depth_downdate(v, L, Wall[(long)k * nW + hi], Wall[(long)k * nW + lo], Sinv[k]);
+      const double L = partial ? partial_L(li, lc) : 1.0;
+      v = onepass_rebuild<1, 4>(v, L, Wall, nW, Sinv, napp, hi, lo);   // (four entries' reads in flight)
       if (i == c) v = D[slot];   // (the diagonal element is current in D, fix_depth's edits included)
       double w = 0.0;
       w += v * H;
@@ -186,26 +118,26 @@ __global__ __launch_bounds__(T) void k_update_depths(StreamArgs a, int M, int or
     __syncthreads();
     // S = H W[c] + R, inverse, gate (every thread: the verdict is uniform)
     const double R = R_all[b * r_stride_b + entry_of(e) * r_stride_m];
-    double S, Si;
+    double S, Si[1];
     {
       double s = 0.0;
       s += H * W[c];
       S = s + R;
     }
-    small_inverse_dev(1, &S, &Si);
+    small_inverse_dev(1, &S, Si);
     double mahal = 0.0;
-    { double t = 0.0; t += res * Si; mahal += t * res; }
+    { double t = 0.0; t += res * Si[0]; mahal += t * res; }
     if (mahal > kGateMahal) { if (res_out) *res_out = 1; continue; }   // :234-239 gated: no fix_depth, no row taken
     int bad = (H != H) ? 1 : 0;
     for (int i = tid; i < nact; i += T) {
-      double k = 0.0;
-      k += W[i] * Si;
-      if (k != k) bad = 1;
+      double k[1];
+      onepass_gains<1>(W, nW, i, Si, k);
+      if (k[0] != k[0]) bad = 1;
     }
     if (bad) *badw = 1;
     __syncthreads();
     bad = *badw;   // (the next writer of the word sits behind the next entry's first barrier)
-    auto gain = [&](int i) { double k = 0.0; k += W[i] * Si; return k; };
+    auto gain = [&](int i) { double k[1]; onepass_gains<1>(W, nW, i, Si, k); return k[0]; };
     if (!bad && tid == 0) {
       double dxb[16], xo[17];
       for (int i = 0; i < 16; i++) {
@@ -216,7 +148,7 @@ __global__ __launch_bounds__(T) void k_update_depths(StreamArgs a, int M, int or
       }
       body_boxplus(xs, dxb, xo);
       for (int i = 0; i < 17; i++) xs[i] = xo[i];
-      Sinv[napp] = Si;
+      Sinv[napp] = Si[0];
     }
     // a thread's features: correction, P(rho, rho), fix_depth and the scan k_update_generic makes when it writes x back
     for (int f = tid; f < len; f += T) {
@@ -236,9 +168,9 @@ __global__ __launch_bounds__(T) void k_update_depths(StreamArgs a, int M, int or
         xf[4] += dv[2];
         const int dr = d + 2;
         const double lr = lam[dr];
-        D[f] = depth_downdate(D[f], partial ? (lr + lr - lr * lr) : 1.0, W[dr], W[dr], Si);
+        D[f] = onepass_apply<1>(D[f], partial ? partial_L(lr, lr) : 1.0, W, nW, Si, dr, dr);
       }
-      fix_depth_lds(f, flag);
+      fix_depth_diag(xs, D, f, prm, flag);
       for (int q = 0; q < 5; q++) {
         const double v = xf[q];
         if (v != v) flag |= FLAG_NAN;
@@ -257,14 +189,9 @@ __global__ __launch_bounds__(T) void k_update_depths(StreamArgs a, int M, int or
   }
   if (!dirty) return;   // every entry skipped, invalid, NaN or gated: the filter is left as it is
   __syncthreads();
-  for (int i = tid; i < nxa; i += T) xg[i] = xs[i];
-  for (int f = tid; f < len; f += T) {   // (fix_depth only: the diagonals it edited and no other)
-    const long dR = dxZ + 3 * f + 2;
-    if (napp > 0 || __double_as_longlong(P[dR + dR * ld]) != __double_as_longlong(D[f])) P[dR + dR * ld] = D[f];
-  }
-  if (flag) atomicOr(&a.flags[b], flag);
+  onepass_store<T>(a, b, xg, P, len, napp, flag, xs, D);
   if (napp == 0) return;
-  depth_trailing<T>(P, ld, nact, nW, napp, partial, Wall, Sinv, lam);
+  onepass_trailing<T, 1>(P, ld, nact, nW, napp, partial, Wall, Sinv, lam);
 }
 
 // The M-launch route of viekf_batch_update_depths: entry m of every filter in the [B] rows k_update_generic reads ...
@@ -286,43 +213,6 @@ __global__ __launch_bounds__(256) void k_depths_scatter(int B, int M, int m, con
   const int b = blockIdx.x * 256 + threadIdx.x;
   if (b >= B) return;
   result[(long)b * M + m] = res_m[b];
-}
-
-// viekf_frame_intake_depth: which entries of a frame are DEPTH measurements, and their slots.  One workgroup of 64 per filter.
-//   slot_out [B][M]: the slot of the entry's id in the intake's table; -1 (viekf_batch_update_depths answers SKIPPED) for an
-//   entry that is no measurement or a filter without a frame; kDepthNoSlot (>= every len_features: INVALID) for an id that is
-//   not in the table, and for every id >= 0 of a filter whose table is stale.   act_out [B][M]: use_depth.
-constexpr int kDepthNoSlot = 0x7fffffff;
-__global__ __launch_bounds__(64) void k_frame_depth_plan(int B, int N, int M, const int* __restrict__ len, const int* __restrict__ tab,
-                                                         const int* __restrict__ tlen, const int* __restrict__ ids,
-                                                         const double* __restrict__ depth, const int* __restrict__ feat_result,
-                                                         const unsigned char* __restrict__ active, int use_depth,
-                                                         int* __restrict__ slot_out, unsigned char* __restrict__ act_out) {
-  const int b = blockIdx.x;
-  if (b >= B) return;
-  const bool act = active ? active[b] != 0 : true;
-  const int tl = tlen[b];
-  const bool stale = len[b] != tl;
-  const int* row = tab + (long)b * N;
-  for (int i = threadIdx.x; i < M; i += 64) {
-    const long at = (long)b * M + i;
-    const int id = ids[at];
-    int slot = -1;
-    if (act && id >= 0) {
-      if (stale) slot = kDepthNoSlot;
-      else {
-        const int fr = feat_result[at];
-        const double d = depth[at];
-        if ((fr == 0 || fr == 1) && d == d && fabs(d) <= 1.7976931348623157e308) {   // queued as FEAT, finite depth
-          slot = kDepthNoSlot;
-          for (int f = 0; f < tl && f < N; f++)
-            if (row[f] == id) { slot = f; break; }
-        }
-      }
-    }
-    slot_out[at] = slot;
-    act_out[at] = use_depth ? (unsigned char)1 : (unsigned char)0;
-  }
 }
 
 }  // namespace viekf

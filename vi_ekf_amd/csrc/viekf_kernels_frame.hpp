@@ -12,6 +12,7 @@
 //                     number of k_init_feature launches leave.
 //   k_frame_finish    one wave64 per filter: the update results back in frame order, merged with the codes the plan
 //                     decided, the gated list, did_reset.
+//   k_frame_slot_plan the id -> slot lookup of the intake's DEPTH and PIXEL_VEL steps, which run behind the intake.
 // Between them run the existing k_keep_features, k_keyframe_reset and the batch's own FEAT update.  Synchronisation is
 // __syncthreads() and wave intrinsics only: no flags, tickets or polling between waves, nothing here can wait for ever.
 #pragma once
@@ -233,6 +234,46 @@ __global__ __launch_bounds__(64) void k_frame_finish(int B, FrameTabs t, int M, 
   if (lane == 0) {
     if (gated_count) gated_count[b] = ng;
     if (did_reset) did_reset[b] = t.rmask[b];
+  }
+}
+
+// viekf_frame_intake_depth / viekf_frame_intake_pixel_vel: which entries of a frame are measurements of the step's kind, and
+// their slots.  One workgroup of 64 per filter; val [B][M][ZD] is what an entry measures (a depth: ZD = 1, a flow: 2).
+//   slot_out [B][M]: the slot of the entry's id in the intake's table; -1 (the update answers SKIPPED) for an entry that is no
+//   measurement or a filter without a frame; kFrameNoSlot (>= every len_features: INVALID) for an id that is not in the table,
+//   and for every id >= 0 of a filter whose table is stale.   act_out [B][M]: use.
+constexpr int kFrameNoSlot = 0x7fffffff;
+template <int ZD>
+__global__ __launch_bounds__(64) void k_frame_slot_plan(int B, int N, int M, const int* __restrict__ len, const int* __restrict__ tab,
+                                                        const int* __restrict__ tlen, const int* __restrict__ ids,
+                                                        const double* __restrict__ val, const int* __restrict__ feat_result,
+                                                        const unsigned char* __restrict__ active, int use, int* __restrict__ slot_out,
+                                                        unsigned char* __restrict__ act_out) {
+  const int b = blockIdx.x;
+  if (b >= B) return;
+  const bool act = active ? active[b] != 0 : true;
+  const int tl = tlen[b];
+  const bool stale = len[b] != tl;
+  const int* row = tab + (long)b * N;
+  for (int i = threadIdx.x; i < M; i += 64) {
+    const long at = (long)b * M + i;
+    const int id = ids[at];
+    int slot = -1;
+    if (act && id >= 0) {
+      if (stale) slot = kFrameNoSlot;
+      else {
+        const int fr = feat_result[at];
+        bool finite = true;   // (false for a NaN)
+        for (int q = 0; q < ZD; q++) finite &= fabs(val[ZD * at + q]) <= 1.7976931348623157e308;
+        if ((fr == 0 || fr == 1) && finite) {   // queued as FEAT, finite measurement
+          slot = kFrameNoSlot;
+          for (int f = 0; f < tl && f < N; f++)
+            if (row[f] == id) { slot = f; break; }
+        }
+      }
+    }
+    slot_out[at] = slot;
+    act_out[at] = use ? (unsigned char)1 : (unsigned char)0;
   }
 }
 

@@ -1,35 +1,30 @@
 // viekf_kernels_pixvel.hpp -- the PIXEL_VEL measurement (viekf_pixvel_model.hpp): the update kernel, one entry per launch, the
-// read-only evaluation, the flow of a frame's features by id and the id -> slot lookup of the intake's pixel-velocity step.
+// read-only evaluation and the flow of a frame's features by id.  (The id -> slot lookup of the intake's pixel-velocity step:
+// k_frame_slot_plan, viekf_kernels_frame.hpp.)
 // Defines kernels: included from viekf_dispatch.hpp only.
 #pragma once
 #include "viekf_kernel_args.hpp"
 #include "viekf_meas_models.hpp"
+#include "viekf_onepass.hpp"
 #include "viekf_pixvel_lds.hpp"
 #include "viekf_pixvel_model.hpp"
 
 namespace viekf {
 
-// The arithmetic both routes share, stated once so that they contract alike: route 1 must give route 0's bits.
-//   L(i, j) of the partial update;  a gain element K[i][q] = sum_p W[i][p] S^-1[p][q];  one element of the correction;
-//   one applied entry's downdate of one element, v -= L (K[hi] . W[lo]) with hi = max(i, j), lo = min(i, j).
-__device__ __forceinline__ double pixvel_L(bool partial, double li, double lj) { return partial ? (lj + li - li * lj) : 1.0; }
+// The arithmetic both routes share is viekf_onepass.hpp's at rank 2, stated once so that they contract alike: route 1 must
+// give route 0's bits.  Route 0 keeps W and K interleaved, so it hands the pairs over by value:
+//   a gain element K[i][q];  one element of the correction;  one applied entry's downdate of one element.
 __device__ __forceinline__ double pixvel_gain(double w0, double w1, const double* Si, int q) {
-  double k = 0.0;
-  k += w0 * Si[q];
-  k += w1 * Si[2 + q];
-  return k;
+  const double w[2] = {w0, w1};
+  return onepass_gain<2>(w, Si, q);
 }
 __device__ __forceinline__ double pixvel_dx(double l, double k0, double k1, double r0, double r1) {
-  double s = 0.0;
-  s += (l * k0) * r0;
-  s += (l * k1) * r1;
-  return s;
+  const double k[2] = {k0, k1}, r[2] = {r0, r1};
+  return onepass_dx<2>(l, k, r);
 }
 __device__ __forceinline__ double pixvel_downdate(double v, double L, double k0, double k1, double w0, double w1) {
-  double t = 0.0;
-  t += k0 * w0;
-  t += k1 * w1;
-  return v - L * t;
+  const double k[2] = {k0, k1}, w[2] = {w0, w1};
+  return onepass_downdate<2>(v, L, k, w);
 }
 // one row of W = P H^T: the nine elements of the row of P that H's columns name (col(c)), times Hc (sm[0 .. 17])
 template <class Col>
@@ -180,7 +175,7 @@ __global__ __launch_bounds__(T) void k_update_pixvel(StreamArgs a, int M, int m,
       for (int i = tid & 63; i < nact; i += 64) {
         const int hi = max(i, j), lo = min(i, j);   // (exactly symmetric result, as k_update_generic)
         const long at = i + (long)j * ld;
-        P[at] = pixvel_downdate(P[at], pixvel_L(partial, lam[i], lj), K[2 * hi], K[2 * hi + 1], W[2 * lo], W[2 * lo + 1]);
+        P[at] = pixvel_downdate(P[at], partial_L(partial, lam[i], lj), K[2 * hi], K[2 * hi + 1], W[2 * lo], W[2 * lo + 1]);
       }
     }
   }
@@ -203,11 +198,9 @@ __global__ __launch_bounds__(T) void k_update_pixvel(StreamArgs a, int M, int m,
 //
 // What an entry needs of the current P is nine columns.  The six body columns (VEL, B_G) ride along as a panel Pb that every
 // applied entry downdates (as section 17 of DESIGN.md keeps its body panel).  The feature's three columns are rebuilt
-// left-looking (section 18): the start P's column, from global memory, which nobody writes before the trailing pass, minus the
-// downdates of the entries applied so far, which their W and S^-1 in LDS give.  fix_depth edits P(rho, rho), which later
-// entries only subtract from: those diagonals ride along in D.  Every other element of the lower triangle gets the applied
-// entries' downdates in entry order in the trailing pass: loaded once, stored once.  Nothing above the diagonal, at or past
-// row / column nact, or in the pad rows is read or written.
+// left-looking (onepass_rebuild<2>): the start P's column, from global memory, which nobody writes before the trailing pass,
+// minus the downdates of the entries applied so far, which their W and S^-1 in LDS give.  The rho diagonals in D, the
+// trailing pass and what is never touched: viekf_onepass.hpp.
 // One workgroup per filter; a.si(b) is followed.  The rules of an entry and their order: include/viekf_pixvel.h.
 // ------------------------------------------------------------------------------------------------
 template <int T>
@@ -239,7 +232,6 @@ __global__ __launch_bounds__(T) void k_update_pixvels(StreamArgs a, int M, int o
   double* P = a.P + a.si(b) * n * ld;
   const int len = a.len[b];
   const int nact = 16 + 3 * len;
-  const int nxa = xZ + 5 * len;
   const bool partial = prm.use_partial_update != 0;
   const long row = (long)b * M;
   const double* gyro = gyro_all + 3L * b;
@@ -248,9 +240,7 @@ __global__ __launch_bounds__(T) void k_update_pixvels(StreamArgs a, int M, int o
   auto p_low = [&](int i, int c) { return (i >= c) ? P[i + (long)c * ld] : P[c + (long)i * ld]; };   // (the lower triangle only)
   const int bcol[6] = {dxVEL, dxVEL + 1, dxVEL + 2, dxB_G, dxB_G + 1, dxB_G + 2};
 
-  for (int i = tid; i < nxa; i += T) xs[i] = xg[i];
-  for (int i = tid; i < n; i += T) lam[i] = a.lambda[i];
-  for (int f = tid; f < len; f += T) { const long dR = dxZ + 3 * f + 2; D[f] = P[dR + dR * ld]; }
+  onepass_load<T>(a, xg, P, len, xs, lam, D);
   for (int i = tid; i < nact; i += T) {
     double v[6];
 #pragma unroll
@@ -258,13 +248,6 @@ __global__ __launch_bounds__(T) void k_update_pixvels(StreamArgs a, int M, int o
 #pragma unroll
     for (int j = 0; j < 6; j++) Pb[j * nW + i] = v[j];
   }
-
-  auto fix_depth_lds = [&](int f, unsigned& flag) {   // fix_depth_one with P(rho, rho) in D
-    const int xR = xZ + 5 * f + 4;
-    double rho = xs[xR];
-    fix_depth_rule(rho, 1.0 / (2.0 * prm.min_depth), flag, [&](double e2) { D[f] += e2; }, [&] { D[f] = prm.P0_feat[2]; });
-    xs[xR] = rho;
-  };
 
   unsigned flag = 0;    // (per thread; ORed into the filter's word at the end)
   int napp = 0;         // entries applied so far: the rows of W / Si the next one writes
@@ -281,7 +264,7 @@ __global__ __launch_bounds__(T) void k_update_pixvels(StreamArgs a, int M, int o
     if (z0 != z0 || z1 != z1 || gyro_nan) { if (res_out) *res_out = 2; continue; }   // MEAS_NAN
     __syncthreads();   // what the load or the entry before wrote (xs, D, Pb, W, Si); sm and Fc are free again
     if (act == 0) {    // :230 -- an inactive measurement only runs fix_depth
-      for (int f = tid; f < len; f += T) fix_depth_lds(f, flag);
+      for (int f = tid; f < len; f += T) fix_depth_diag(xs, D, f, prm, flag);
       if (res_out) *res_out = 0;
       dirty = true;
       continue;
@@ -301,12 +284,8 @@ __global__ __launch_bounds__(T) void k_update_pixvels(StreamArgs a, int M, int o
       const int c = cols[6 + q];
       double v = p_low(i, c);
       const int hi = max(i, c), lo = min(i, c);
-      const double L = pixvel_L(partial, lam[i], lam[c]);
-      for (int k = 0; k < napp; k++) {
-        const double* Wk = Wall + (long)k * 2 * nW;
-        const double* Sk = Sinv + 4 * k;
-        v = pixvel_downdate(v, L, pixvel_gain(Wk[hi], Wk[nW + hi], Sk, 0), pixvel_gain(Wk[hi], Wk[nW + hi], Sk, 1), Wk[lo], Wk[nW + lo]);
-      }
+      const double L = partial_L(partial, lam[i], lam[c]);
+      v = onepass_rebuild<2, 1>(v, L, Wall, nW, Sinv, napp, hi, lo);
       if (q == 2 && i == c) v = D[slot];   // (the rho diagonal is current in D, fix_depth's edits included)
       Fc[q * nW + i] = v;
     }
@@ -349,9 +328,7 @@ __global__ __launch_bounds__(T) void k_update_pixvels(StreamArgs a, int M, int o
       for (int idx = tid; idx < 6 * nact; idx += T) {
         const int j = idx / nact, i = idx - j * nact;
         const int c = bcol[j];
-        const int hi = max(i, c), lo = min(i, c);
-        Pb[j * nW + i] = pixvel_downdate(Pb[j * nW + i], pixvel_L(partial, lam[i], lam[c]), pixvel_gain(W0[hi], W1[hi], Si, 0),
-                                         pixvel_gain(W0[hi], W1[hi], Si, 1), W0[lo], W1[lo]);
+        Pb[j * nW + i] = onepass_apply<2>(Pb[j * nW + i], partial_L(partial, lam[i], lam[c]), W0, nW, Si, max(i, c), min(i, c));
       }
     }
     // a thread's features: correction, P(rho, rho), fix_depth and the scan k_update_pixvel makes when it writes x back
@@ -367,10 +344,9 @@ __global__ __launch_bounds__(T) void k_update_pixvels(StreamArgs a, int M, int o
         xf[0] = qn[0]; xf[1] = qn[1]; xf[2] = qn[2]; xf[3] = qn[3];
         xf[4] += dv[2];
         const int dr = d + 2;
-        D[f] = pixvel_downdate(D[f], pixvel_L(partial, lam[dr], lam[dr]), pixvel_gain(W0[dr], W1[dr], Si, 0),
-                               pixvel_gain(W0[dr], W1[dr], Si, 1), W0[dr], W1[dr]);
+        D[f] = onepass_apply<2>(D[f], partial_L(partial, lam[dr], lam[dr]), W0, nW, Si, dr, dr);
       }
-      fix_depth_lds(f, flag);
+      fix_depth_diag(xs, D, f, prm, flag);
       for (int q = 0; q < 5; q++) {
         const double v = xf[q];
         if (v != v) flag |= FLAG_NAN;
@@ -389,52 +365,9 @@ __global__ __launch_bounds__(T) void k_update_pixvels(StreamArgs a, int M, int o
   }
   if (!dirty) return;   // every entry skipped, invalid, NaN or gated: the filter is left as it is
   __syncthreads();
-  for (int i = tid; i < nxa; i += T) xg[i] = xs[i];
-  for (int f = tid; f < len; f += T) {   // (fix_depth only: the diagonals it edited and no other)
-    const long dR = dxZ + 3 * f + 2;
-    if (napp > 0 || __double_as_longlong(P[dR + dR * ld]) != __double_as_longlong(D[f])) P[dR + dR * ld] = D[f];
-  }
-  if (flag) atomicOr(&a.flags[b], flag);
+  onepass_store<T>(a, b, xg, P, len, napp, flag, xs, D);
   if (napp == 0) return;
-  // ---- the trailing pass: the lower triangle of the active block, rho diagonals excepted.  A lane keeps ROW i (64 consecutive
-  //      rows per wave: a column's segment is 512 contiguous bytes); a wave takes UN adjacent columns at a time, loads before
-  //      arithmetic; the entries run innermost, in order, on the values held in registers ----
-  constexpr int NWV = T / 64, UN = 8;
-  const int wid = tid >> 6, lane = tid & 63;
-  for (int r0 = 0; r0 < nact; r0 += 64) {
-    const int i = r0 + lane;
-    const bool valid = i < nact;
-    const int ir = valid ? i : 0;
-    const double li = lam[ir];
-    const bool isrho = i >= dxZ && (i - dxZ) % 3 == 2;
-    const int jend = min(r0 + 63, nact - 1);
-    for (int j0 = wid * UN; j0 <= jend; j0 += NWV * UN) {
-      double p[UN], L[UN];
-      bool ok[UN];
-#pragma unroll
-      for (int u = 0; u < UN; u++) {
-        const int j = j0 + u;
-        ok[u] = valid && j <= i && !(i == j && isrho);   // (j <= i < nact)
-        p[u] = 0.0;
-        if (ok[u]) p[u] = P[i + (long)j * ld];
-      }
-#pragma unroll
-      for (int u = 0; u < UN; u++) L[u] = pixvel_L(partial, li, lam[min(j0 + u, nact - 1)]);
-      for (int k = 0; k < napp; k++) {
-        const double* Wk = Wall + (long)k * 2 * nW;
-        const double* Sk = Sinv + 4 * k;
-        const double k0 = pixvel_gain(Wk[ir], Wk[nW + ir], Sk, 0), k1 = pixvel_gain(Wk[ir], Wk[nW + ir], Sk, 1);
-#pragma unroll
-        for (int u = 0; u < UN; u++) {
-          const int jc = min(j0 + u, nact - 1);
-          p[u] = pixvel_downdate(p[u], L[u], k0, k1, Wk[jc], Wk[nW + jc]);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < UN; u++)
-        if (ok[u]) P[i + (long)(j0 + u) * ld] = p[u];
-    }
-  }
+  onepass_trailing<T, 2>(P, ld, nact, nW, napp, partial, Wall, Sinv, lam);
 }
 
 // viekf_batch_eval_pixel_vel: zhat [B][2] and, where H is not NULL, H [B][2][n] dense, at the batch's current state -- the device
@@ -494,44 +427,6 @@ __global__ __launch_bounds__(64) void k_pixel_flow(int B, int Mp, const double* 
     }
     zdot[2 * at] = o0;
     zdot[2 * at + 1] = o1;
-  }
-}
-
-// viekf_frame_intake_pixel_vel: which entries of a frame are PIXEL_VEL measurements, and their slots.  One workgroup of 64 per
-// filter.  slot_out [B][M]: the slot of the entry's id in the intake's table; -1 (the update answers SKIPPED) for an entry that
-// is no measurement or a filter without a frame; kPixvelNoSlot (>= every len_features: INVALID) for an id that is not in the
-// table, and for every id >= 0 of a filter whose table is stale.   act_out [B][M]: use_pixel_vel.
-constexpr int kPixvelNoSlot = 0x7fffffff;
-__global__ __launch_bounds__(64) void k_frame_pixvel_plan(int B, int N, int M, const int* __restrict__ len, const int* __restrict__ tab,
-                                                          const int* __restrict__ tlen, const int* __restrict__ ids,
-                                                          const double* __restrict__ zdot, const int* __restrict__ feat_result,
-                                                          const unsigned char* __restrict__ active, int use_pixel_vel,
-                                                          int* __restrict__ slot_out, unsigned char* __restrict__ act_out) {
-  const int b = blockIdx.x;
-  if (b >= B) return;
-  const bool act = active ? active[b] != 0 : true;
-  const int tl = tlen[b];
-  const bool stale = len[b] != tl;
-  const int* row = tab + (long)b * N;
-  const double big = 1.7976931348623157e308;
-  for (int i = threadIdx.x; i < M; i += 64) {
-    const long at = (long)b * M + i;
-    const int id = ids[at];
-    int slot = -1;
-    if (act && id >= 0) {
-      if (stale) slot = kPixvelNoSlot;
-      else {
-        const int fr = feat_result[at];
-        const double d0 = zdot[2 * at], d1 = zdot[2 * at + 1];
-        if ((fr == 0 || fr == 1) && fabs(d0) <= big && fabs(d1) <= big) {   // queued as FEAT, finite flow
-          slot = kPixvelNoSlot;
-          for (int f = 0; f < tl && f < N; f++)
-            if (row[f] == id) { slot = f; break; }
-        }
-      }
-    }
-    slot_out[at] = slot;
-    act_out[at] = use_pixel_vel ? (unsigned char)1 : (unsigned char)0;
   }
 }
 

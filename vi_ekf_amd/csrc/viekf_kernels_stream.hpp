@@ -14,6 +14,7 @@
 // carve-ups of k_propagate_stream and k_update_feat_stream viekf_stream_lds.hpp (BlkLds, the grouped update's, is below).
 #pragma once
 #include "viekf_kernel_args.hpp"
+#include "viekf_onepass.hpp"
 #include "viekf_stream_lds.hpp"
 
 namespace viekf {
@@ -755,12 +756,7 @@ __global__ __launch_bounds__(T) void k_update_feat_blocked(StreamArgs a, const d
       }
     };
     auto fix_depth_own = [&]() {                            // fix_depth (:271) on the state and the running diagonal
-      for (int f = tid; f < len; f += T) {
-        const int xR = xZ + 5 * f + 4;
-        double rho = xs[xR];
-        fix_depth_rule(rho, 1.0 / (2.0 * prm.min_depth), flag, [&](double e2) { diag[f] += e2; }, [&] { diag[f] = prm.P0_feat[2]; });
-        xs[xR] = rho;
-      }
+      for (int f = tid; f < len; f += T) fix_depth_diag(xs, diag, f, prm, flag);
     };
     publish_pzz(0);   // (own row: written by this thread in the load above)
     __syncthreads();
