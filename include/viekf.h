@@ -4,9 +4,11 @@
  * The reference has no C ABI or plugin registry: its boundary is the C++ class
  * vi_ekf::VIEKF (reference include/vi_ekf.h:82-338).  Every entry point below
  * names the VIEKF member it replaces (file:line relative to the reference
- * tree).  One viekf_batch holds `batch` independent filters that share one
- * parameter set and one capacity `num_features` (the reference's compile-time
- * NUM_FEATURES, include/vi_ekf.h:39-48, is a run-time value here):
+ * tree).  One viekf_batch holds `batch` independent filters of one capacity
+ * `num_features` (the reference's compile-time NUM_FEATURES,
+ * include/vi_ekf.h:39-48, is a run-time value here).  They start on the one
+ * parameter set the batch is created with and may each be given a set of their
+ * own (viekf_batch_set_params_filters):
  *     nx = 17 + 5*num_features   (MAX_X)      n = 16 + 3*num_features  (MAX_DX)
  *
  * Array conventions (all caller-owned, never retained past the call):
@@ -113,6 +115,27 @@ int viekf_batch_destroy(viekf_batch *b);
 int viekf_batch_reset(viekf_batch *b);    /* back to the state viekf_batch_create left */
 int viekf_batch_dims(const viekf_batch *b, int32_t *batch, int32_t *num_features, int32_t *nx, int32_t *n);
 int viekf_batch_get_params(const viekf_batch *b, viekf_params *out);   /* the parameter set the batch was created with */
+/* PER-FILTER PARAMETER SETS: a different camera, extrinsics and noise per filter (one platform or one point of a sweep each).
+ * p [batch] in HOST memory, entry f for filter f; NULL = back to the set the batch was created with.
+ *   Effect.  The sets hold for every launch queued after the call, in stream order.  The live x and P are not touched: x0, P0
+ *     and P0_feat are seen by the next viekf_batch_reset (filter f goes to ITS x0 and diag(P0 | P0_feat ...)), P0_feat also by
+ *     init_feature / the frame intake's new features.
+ *   Structural fields stay the batch's.  In every entry use_drag_term (the CURRENT value of the run-time switch,
+ *     viekf_batch_get_drag_term), use_partial_update, use_keyframe_reset and keyframe_overlap_threshold must equal the batch's:
+ *     otherwise VIEKF_ERR_INVALID, viekf_last_error names the filter and the field, and nothing changes.  (use_drag_term
+ *     decides zdim of ACC on the host and the keyframe threshold is one value per frame-intake launch.)
+ *     viekf_batch_set_drag_term keeps switching every filter's set.
+ *   Value checks.  An entry passes exactly the value checks viekf_batch_create makes of a set.
+ *   viekf_batch_get_params keeps returning the creation set; viekf_batch_get_params_filter returns filter f's current set
+ *     (the creation set, with the current drag switch, while no per-filter sets are in force).
+ *   Parameters are not part of a ring slot: snapshot / restore / select do not move them, and the call is legal under
+ *     viekf_batch_select, viekf_batch_select_filters and a participation mask.
+ *   The kernels specialised for lambda_feat = [1, 1, x] (VIEKF_TUNE_UNIT_LAMBDA) are used only if EVERY filter's set allows them.
+ *   A sequencer (viekf_seq_create, viekf_seq_create_independent) copies every filter's set when it is created -- it rotates the
+ *     stored inputs with filter f's q_b_u on the host --: sets given to the core afterwards are not seen by that sequencer.
+ *   The simulator, the camera model and the KLT tracker keep parameter copies of their own. */
+int viekf_batch_set_params_filters(viekf_batch *b, const viekf_params *p);
+int viekf_batch_get_params_filter(const viekf_batch *b, int32_t filter, viekf_params *out);
 /* run all later calls of this batch on a caller-owned hipStream_t (e.g. torch's current stream);
  * NULL = HIP's default (null) stream.  A new batch starts on a private non-blocking stream. */
 int viekf_batch_set_stream(viekf_batch *b, void *hip_stream);

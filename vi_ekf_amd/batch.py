@@ -15,7 +15,14 @@ from ._dev import is_torch, r_colmajor
 
 class BatchVIEKF:
     def __init__(self, batch, num_features, params, device=0):
+        """params: one parameter set (dict or capi.Params) for every filter, or a list of `batch` of them, one per filter: the
+        batch is then created with entry 0, given the list (set_params) and reset, so that filter b starts at ITS x0 / P0."""
         L = capi.lib()
+        per_filter = None
+        if isinstance(params, (list, tuple)):
+            if len(params) != int(batch):
+                raise ValueError("a list of parameter sets needs one entry per filter: %d, got %d" % (int(batch), len(params)))
+            per_filter, params = params, params[0]
         if isinstance(params, dict):
             params = capi.Params.from_dict(params)
         self.params = params
@@ -25,6 +32,13 @@ class BatchVIEKF:
         self.nx, self.n = 17 + 5 * self.N, 16 + 3 * self.N
         self.device = int(device)
         self._keep = []
+        if per_filter is not None:
+            try:
+                self.set_params(per_filter)
+                self.reset()
+            except Exception:
+                self.close()
+                raise
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -95,6 +109,34 @@ class BatchVIEKF:
 
     def reset(self):
         capi.check(capi.lib().viekf_batch_reset(self._h))
+
+    def set_drag_term(self, use_drag_term):
+        """the run-time drag switch (viekf_batch_set_drag_term): every filter's parameter set follows it"""
+        capi.check(capi.lib().viekf_batch_set_drag_term(self._h, int(bool(use_drag_term))))
+
+    def get_drag_term(self):
+        out = C.c_int32(0)
+        capi.check(capi.lib().viekf_batch_get_drag_term(self._h, C.byref(out)))
+        return bool(out.value)
+
+    def set_params(self, params):
+        """one parameter set per filter (viekf_batch_set_params_filters): a list of `batch` dicts or capi.Params; None = back to the
+        set the batch was created with.  Holds for every launch after the call; x0 / P0 are seen by the next reset()."""
+        if params is None:
+            capi.check(capi.lib().viekf_batch_set_params_filters(self._h, None))
+            return
+        if len(params) != self.B:
+            raise ValueError("a list of parameter sets needs one entry per filter: %d, got %d" % (self.B, len(params)))
+        arr = (capi.Params * self.B)()
+        for b, p in enumerate(params):
+            arr[b] = capi.Params.from_dict(p) if isinstance(p, dict) else p
+        capi.check(capi.lib().viekf_batch_set_params_filters(self._h, arr))
+
+    def params_of(self, b):
+        """-> capi.Params: filter b's current parameter set (viekf_batch_get_params_filter)"""
+        p = capi.Params()
+        capi.check(capi.lib().viekf_batch_get_params_filter(self._h, int(b), C.byref(p)))
+        return p
 
     def get_state(self):
         """-> x [B][nx] (reference get_state(), include/vi_ekf.h:277)"""

@@ -35,6 +35,7 @@ SYMBOLS = [
     "viekf_seq_propagate_state", "viekf_seq_set_x0", "viekf_seq_set_imu_bias", "viekf_seq_keyframe_reset",
     "viekf_seq_get_features", "viekf_seq_get_feat", "viekf_seq_drop_features", "viekf_seq_add_frame", "viekf_batch_set_async",
     "viekf_batch_select_filters", "viekf_batch_propagate_filters_to", "viekf_batch_propagate_n_filters_to",
+    "viekf_batch_set_params_filters", "viekf_batch_get_params_filter",
 ]
 
 # what include/viekf_body.h declares (the fused body-sensor update: BatchVIEKF.update_body)
@@ -132,6 +133,9 @@ def lib():
         L.viekf_batch_destroy.argtypes = [_vp]
         L.viekf_batch_reset.argtypes = [_vp]
         L.viekf_batch_dims.argtypes = [_vp] + [C.POINTER(C.c_int32)] * 4
+        L.viekf_batch_get_params.argtypes = [_vp, C.POINTER(Params)]
+        L.viekf_batch_set_params_filters.argtypes = [_vp, C.POINTER(Params)]   # [batch] entries, or None
+        L.viekf_batch_get_params_filter.argtypes = [_vp, C.c_int32, C.POINTER(Params)]
         L.viekf_batch_describe.argtypes = [_vp, C.c_char_p, C.c_int32]
         L.viekf_batch_set_stream.argtypes = [_vp, _vp]
         L.viekf_batch_sync.argtypes = [_vp]

@@ -36,6 +36,14 @@ struct viekf_batch {
   size_t res_lds = 0;
   DevParams dp;
   DevParams* d_dp = nullptr;
+  // Per-filter parameter sets (viekf_batch_set_params_filters).  Allocated by the first call that asks for them; pf_on says whether
+  // the launches read them (StreamArgs::pstride = 1) or the one set above.
+  bool pf_on = false;
+  std::vector<viekf_params> pf_params;   // [B] host copy (what viekf_batch_get_params_filter returns)
+  std::vector<DevParams> pf_dp;          // [B] host mirror of pf_d_dp
+  DevParams* pf_d_dp = nullptr;          // [B]
+  double *pf_d_Qx = nullptr, *pf_d_lambda = nullptr, *pf_d_Pdiag = nullptr;   // [B][n]
+  double* pf_d_x0 = nullptr;             // [B][nxs]
   // form of P between launches, which buffer holds the live state, per-filter mode (viekf_pform.hpp); d_x / d_P follow it
   // through point_live() below
   PBook book;
@@ -91,10 +99,11 @@ StreamArgs make_args(const viekf_batch* b, const unsigned char* call_mask = null
   a.smap_out = nullptr;
   a.kcount = nullptr;
   a.x =b->d_x; a.P = b->d_P; a.len = b->d_len; a.flags = b->d_flags;
-  a.Qx = b->d_Qx; a.lambda = b->d_lambda; a.ws = b->d_ws;
+  a.Qx = b->pf_on ? b->pf_d_Qx : b->d_Qx; a.lambda = b->pf_on ? b->pf_d_lambda : b->d_lambda; a.ws = b->d_ws;
   a.B = b->B; a.N = b->N; a.nx = b->nx; a.nxs = b->nxs; a.n = b->n; a.ld = b->ld;
   a.ws_stride = b->ws_stride;
-  a.dp = b->d_dp;
+  a.dp = b->pf_on ? b->pf_d_dp : b->d_dp;
+  a.pstride = b->pf_on ? 1 : 0;
   a.x_out = b->d_x; a.P_out = b->d_P;
   a.active = call_mask ? call_mask : (b->active_on ? b->d_active : nullptr);
   a.resmap = b->d_resmap;
@@ -119,5 +128,10 @@ void point_live(viekf_batch* b) {
 
 // lambda = 1 on the bearing components, or no partial update at all: the fused kernel's unit-Lambda (ZU) instances apply
 bool unit_lambda(const viekf_params& p) { return !p.use_partial_update || (p.lambda_feat[0] == 1.0 && p.lambda_feat[1] == 1.0); }
+// ... for every set a launch of this batch may read
+bool unit_lambda(const viekf_batch* b) {
+  if (!b->pf_on) return unit_lambda(b->params);
+  return std::all_of(b->pf_params.begin(), b->pf_params.end(), [](const viekf_params& p) { return unit_lambda(p); });
+}
 
 }  // namespace

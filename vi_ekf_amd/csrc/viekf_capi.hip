@@ -26,6 +26,36 @@ int viekf::set_last_error(int code, const std::string& msg) {
   return code;
 }
 
+namespace {
+
+// the device-side form of a parameter set
+void fill_dev_params(DevParams& d, const viekf_params& p) {
+  std::memcpy(d.Qu, p.Qu, sizeof d.Qu);
+  std::memcpy(d.P0_feat, p.P0_feat, sizeof d.P0_feat);
+  std::memcpy(d.cam_center, p.cam_center, sizeof d.cam_center);
+  std::memcpy(d.focal, p.focal_len, sizeof d.focal);
+  std::memcpy(d.q_b_c, p.q_b_c, sizeof d.q_b_c);
+  std::memcpy(d.p_b_c, p.p_b_c, sizeof d.p_b_c);
+  std::memcpy(d.q_b_u, p.q_b_u, sizeof d.q_b_u);
+  d.min_depth = p.min_depth;
+  d.use_drag_term = p.use_drag_term;
+  d.use_partial_update = p.use_partial_update;
+  for (int i = 0; i < 6; i++) d.sqrtQu[i] = std::sqrt(p.Qu[i] > 0.0 ? p.Qu[i] : 0.0);
+}
+
+// a set's vectors over the n error-state rows: Qx diag, lambda, initial P diagonal (vi_ekf.cpp:134-146)
+void fill_row_vectors(const viekf_params& p, int N, double* Qx, double* lam, double* Pd) {
+  for (int i = 0; i < 16; i++) { Qx[i] = p.Qx[i]; lam[i] = p.lambda[i]; Pd[i] = p.P0[i]; }
+  for (int i = 0; i < N; i++)
+    for (int k = 0; k < 3; k++) {
+      Qx[16 + 3 * i + k] = p.Qx_feat[k];
+      lam[16 + 3 * i + k] = p.lambda_feat[k];
+      Pd[16 + 3 * i + k] = p.P0_feat[k];
+    }
+}
+
+}  // namespace
+
 extern "C" {
 
 int viekf_abi_version(void) { return VIEKF_ABI_VERSION; }
@@ -118,18 +148,7 @@ int viekf_batch_create(int32_t batch, int32_t num_features, const viekf_params* 
   // of each on one box: 239 instead of 226 MB of P next to the 256 MiB Infinity Cache): it keeps the dense stride.
   b->ld = cov_ld(num_features);   // (N > 77: columns on whole lines; viekf_host.hpp)
   b->params = *p;
-  DevParams& d = b->dp;
-  std::memcpy(d.Qu, p->Qu, sizeof d.Qu);
-  std::memcpy(d.P0_feat, p->P0_feat, sizeof d.P0_feat);
-  std::memcpy(d.cam_center, p->cam_center, sizeof d.cam_center);
-  std::memcpy(d.focal, p->focal_len, sizeof d.focal);
-  std::memcpy(d.q_b_c, p->q_b_c, sizeof d.q_b_c);
-  std::memcpy(d.p_b_c, p->p_b_c, sizeof d.p_b_c);
-  std::memcpy(d.q_b_u, p->q_b_u, sizeof d.q_b_u);
-  d.min_depth = p->min_depth;
-  d.use_drag_term = p->use_drag_term;
-  d.use_partial_update = p->use_partial_update;
-  for (int i = 0; i < 6; i++) d.sqrtQu[i] = std::sqrt(p->Qu[i] > 0.0 ? p->Qu[i] : 0.0);
+  fill_dev_params(b->dp, *p);
   const WsLayout L(b->N, b->n);
   b->ws_stride = L.total;
   DevOwner& own = b->own;
@@ -157,13 +176,7 @@ int viekf_batch_create(int32_t batch, int32_t num_features, const viekf_params* 
   b->own_stream = true;
   // shared per-batch vectors: Qx diag, lambda, initial P diagonal (vi_ekf.cpp:134-146)
   std::vector<double> Qx(b->n), lam(b->n), Pd(b->n);
-  for (int i = 0; i < 16; i++) { Qx[i] = p->Qx[i]; lam[i] = p->lambda[i]; Pd[i] = p->P0[i]; }
-  for (int i = 0; i < b->N; i++)
-    for (int k = 0; k < 3; k++) {
-      Qx[16 + 3 * i + k] = p->Qx_feat[k];
-      lam[16 + 3 * i + k] = p->lambda_feat[k];
-      Pd[16 + 3 * i + k] = p->P0_feat[k];
-    }
+  fill_row_vectors(*p, b->N, Qx.data(), lam.data(), Pd.data());
   auto up = [&](double* dptr, const double* h, size_t cnt) {
     if (hipMemcpy(dptr, h, cnt * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = VIEKF_ERR_HIP;
   };
@@ -199,7 +212,10 @@ int viekf_batch_reset(viekf_batch* b) {
   if (int rc = check_batch(b)) return rc;
   HIP_TRY(hipSetDevice(b->device));
   StreamArgs a = make_args(b);
-  hipLaunchKernelGGL(k_reset, dim3(b->B), dim3(256), 0, b->stream, a, b->d_x0, b->d_Pdiag);
+  if (b->pf_on)
+    hipLaunchKernelGGL(k_reset, dim3(b->B), dim3(256), 0, b->stream, a, b->pf_d_x0, b->pf_d_Pdiag, (long)b->nxs, (long)b->n);
+  else
+    hipLaunchKernelGGL(k_reset, dim3(b->B), dim3(256), 0, b->stream, a, b->d_x0, b->d_Pdiag, 0L, 0L);
   HIP_TRY(hipGetLastError());
   b->book.wrote_live(PForm::Full);   // (k_reset writes all of P)
   HIP_TRY(hipStreamSynchronize(b->stream));
@@ -249,6 +265,64 @@ int viekf_batch_describe(const viekf_batch* b, char* out, int32_t cap) {
 int viekf_batch_get_params(const viekf_batch* b, viekf_params* out) {
   if (!b || !out) return fail(VIEKF_ERR_INVALID, "null argument");
   *out = b->params;
+  return VIEKF_OK;
+}
+
+int viekf_batch_get_params_filter(const viekf_batch* b, int32_t filter, viekf_params* out) {
+  if (!b || !out) return fail(VIEKF_ERR_INVALID, "null argument");
+  if (filter < 0 || filter >= b->B) return fail(VIEKF_ERR_INVALID, "get_params_filter: filter index out of range");
+  *out = b->pf_on ? b->pf_params[(size_t)filter] : b->params;
+  return VIEKF_OK;
+}
+
+int viekf_batch_set_params_filters(viekf_batch* b, const viekf_params* p) {
+  if (int rc = check_batch(b)) return rc;
+  HIP_TRY(hipSetDevice(b->device));
+  if (!p) {   // back to the creation set: launches from here on read the batch's one set again (the arguments say which)
+    b->pf_on = false;
+    b->res_zu = b->tune_unit_lambda && unit_lambda(b);
+    return VIEKF_OK;
+  }
+  const size_t Bz = (size_t)b->B, nz = (size_t)b->n, xz = (size_t)b->nxs;
+  for (size_t f = 0; f < Bz; f++) {   // every entry is checked before anything changes
+    const char* field = nullptr;
+    if ((p[f].use_drag_term != 0) != (b->params.use_drag_term != 0)) field = "use_drag_term";
+    else if ((p[f].use_partial_update != 0) != (b->params.use_partial_update != 0)) field = "use_partial_update";
+    else if ((p[f].use_keyframe_reset != 0) != (b->params.use_keyframe_reset != 0)) field = "use_keyframe_reset";
+    else if (!(p[f].keyframe_overlap_threshold == b->params.keyframe_overlap_threshold)) field = "keyframe_overlap_threshold";
+    if (field)
+      return fail(VIEKF_ERR_INVALID, "set_params_filters: filter " + std::to_string(f) + ": " + field +
+                                         " differs from the batch's (structural fields are one value per batch)");
+  }
+  if (!b->pf_d_dp) {   // first use: a batch that never asks for per-filter sets pays nothing
+    DevParams* d_dp = nullptr;
+    double *d_Qx = nullptr, *d_lam = nullptr, *d_Pd = nullptr, *d_x0 = nullptr;
+    int rc = b->own.alloc(&d_dp, Bz);
+    if (!rc) rc = b->own.alloc(&d_Qx, Bz * nz);
+    if (!rc) rc = b->own.alloc(&d_lam, Bz * nz);
+    if (!rc) rc = b->own.alloc(&d_Pd, Bz * nz);
+    if (!rc) rc = b->own.alloc(&d_x0, Bz * xz);
+    if (rc) return rc;   // (what was allocated stays the owner's until destroy; the batch is unchanged)
+    b->pf_d_dp = d_dp; b->pf_d_Qx = d_Qx; b->pf_d_lambda = d_lam; b->pf_d_Pdiag = d_Pd; b->pf_d_x0 = d_x0;
+  }
+  std::vector<DevParams> dps(Bz);
+  std::vector<double> Qx(Bz * nz), lam(Bz * nz), Pd(Bz * nz), x0(Bz * xz, 0.0);
+  for (size_t f = 0; f < Bz; f++) {
+    fill_dev_params(dps[f], p[f]);
+    fill_row_vectors(p[f], b->N, &Qx[f * nz], &lam[f * nz], &Pd[f * nz]);
+    std::memcpy(&x0[f * xz], p[f].x0, sizeof p[f].x0);
+  }
+  // in stream order behind the launches already queued (they may be reading the previous sets from these buffers)
+  HIP_TRY(hipMemcpyAsync(b->pf_d_dp, dps.data(), Bz * sizeof(DevParams), hipMemcpyHostToDevice, b->stream));
+  HIP_TRY(hipMemcpyAsync(b->pf_d_Qx, Qx.data(), Bz * nz * sizeof(double), hipMemcpyHostToDevice, b->stream));
+  HIP_TRY(hipMemcpyAsync(b->pf_d_lambda, lam.data(), Bz * nz * sizeof(double), hipMemcpyHostToDevice, b->stream));
+  HIP_TRY(hipMemcpyAsync(b->pf_d_Pdiag, Pd.data(), Bz * nz * sizeof(double), hipMemcpyHostToDevice, b->stream));
+  HIP_TRY(hipMemcpyAsync(b->pf_d_x0, x0.data(), Bz * xz * sizeof(double), hipMemcpyHostToDevice, b->stream));
+  HIP_TRY(hipStreamSynchronize(b->stream));   // (pageable host memory: the copies have read it when this returns)
+  b->pf_params.assign(p, p + Bz);
+  b->pf_dp.swap(dps);
+  b->pf_on = true;
+  b->res_zu = b->tune_unit_lambda && unit_lambda(b);
   return VIEKF_OK;
 }
 
@@ -302,7 +376,7 @@ int viekf_batch_set_tuning(viekf_batch* b, int32_t key, int32_t value) {
       return VIEKF_OK;
     case VIEKF_TUNE_UNIT_LAMBDA:
       b->tune_unit_lambda = value != 0;
-      b->res_zu = b->tune_unit_lambda && unit_lambda(b->params);
+      b->res_zu = b->tune_unit_lambda && unit_lambda(b);
       return VIEKF_OK;
     case VIEKF_TUNE_BLOCK_GROUP:
       if (value != 0 && value != 16 && value != 24 && value != 32) return fail(VIEKF_ERR_INVALID, "group size must be 0 (auto), 16, 24 or 32");
@@ -548,6 +622,11 @@ int viekf_batch_set_drag_term(viekf_batch* b, int32_t use_drag_term) {
   b->dp.use_drag_term = use_drag_term != 0;
   // (every kernel reads the flag from the device-resident parameter block at launch: ordered on the batch's stream)
   HIP_TRY(hipMemcpyAsync(b->d_dp, &b->dp, sizeof(DevParams), hipMemcpyHostToDevice, b->stream));
+  if (!b->pf_dp.empty()) {   // every filter's set (in force or not: viekf_batch_set_params_filters(NULL) keeps the buffers)
+    for (auto& d : b->pf_dp) d.use_drag_term = use_drag_term != 0;
+    for (auto& q : b->pf_params) q.use_drag_term = use_drag_term != 0;
+    HIP_TRY(hipMemcpyAsync(b->pf_d_dp, b->pf_dp.data(), b->pf_dp.size() * sizeof(DevParams), hipMemcpyHostToDevice, b->stream));
+  }
   HIP_TRY(hipStreamSynchronize(b->stream));   // (b->dp is pageable host memory: the copy has read it when this returns)
   return VIEKF_OK;
 }

@@ -13,7 +13,7 @@ constexpr int xPOS = 0, xVEL = 3, xATT = 6, xB_A = 10, xB_G = 13, xMU = 16, xZ =
 constexpr int dxPOS = 0, dxVEL = 3, dxATT = 6, dxB_A = 9, dxB_G = 12, dxMU = 15, dxZ = 16;  // :103-111
 constexpr double kGravity = 9.80665;  // include/vi_ekf.h:70-74
 
-struct DevParams {  // shared by every filter of a batch (kernel argument, lives in SGPRs/constant)
+struct DevParams {  // one per batch, or one per filter (StreamArgs::prm); device memory, read with uniform loads
   double Qu[6];
   double P0_feat[3];
   double cam_center[2];

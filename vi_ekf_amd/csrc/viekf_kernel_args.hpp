@@ -12,12 +12,14 @@ struct StreamArgs {
   double* P;            // [B][n][ld]
   int* len;             // [B]
   unsigned* flags;      // [B]
-  const double* Qx;     // [n] diagonal
-  const double* lambda; // [n]
+  const double* Qx;     // [n] diagonal, or [B][n] (pstride = 1); read through qx(b) only
+  const double* lambda; // [n], or [B][n]; read through lam(b) only
   double* ws;           // [B][ws_stride]
   int B, N, nx, nxs, n, ld;
   long ws_stride;
   const DevParams* dp;  // device memory (uniform loads); NOT by value: indexing a by-value kernarg array spills it to scratch
+                        // one set, or [B] of them (pstride = 1); read through prm(b) only
+  int pstride;          // 0: the batch's one parameter set; 1: one set per filter (viekf_batch_set_params_filters)
   double* x_out;        // where the fused-step kernel stores the state / covariance: the same buffers (in place) or another
   double* P_out;        // slot of the history ring (viekf_batch_propagate_to: the propagate writes the NEXT slot, no copy)
   const unsigned char* active;   // [B] or NULL: filters with active[b] == 0 take no part in a propagate / feature-update launch
@@ -31,9 +33,19 @@ struct StreamArgs {
   // [B] or NULL: propagates of THIS launch per filter (viekf_batch_propagate_n_filters_to; >= 1 for every filter that takes part).
   // Read by the multi-propagate instances of the fused kernel only; NULL = the launch-wide count of the launch word.
   const int* kcount;
+  // Filter b's parameter set.  With pstride == 0 every address is the shared set's.  b is the workgroup's filter wherever a
+  // workgroup serves one filter, so the loads stay scalar; where the compiler cannot see that (two filters per workgroup) the
+  // caller passes uniform_filter(b).
+  __device__ __forceinline__ const DevParams& prm(int b) const { return dp[(long)b * pstride]; }
+  __device__ __forceinline__ const double* qx(int b) const { return Qx + (long)b * pstride * n; }
+  __device__ __forceinline__ const double* lam(int b) const { return lambda + (long)b * pstride * n; }
   __device__ __forceinline__ long si(int b) const { return smap ? (long)smap[b] : (long)b; }
   __device__ __forceinline__ long so(int b) const { return smap_out ? (long)smap_out[b] : si(b); }
 };
+
+// b as a value the compiler knows to be the same in every lane of the wave (the wave's filter): parameter loads indexed by it stay
+// scalar loads
+__device__ __forceinline__ int uniform_filter(int b) { return __builtin_amdgcn_readfirstlane(b); }
 
 constexpr int WK = 40;   // contraction depth of the low-rank part (16 + 16 + 6, padded to whole MFMA k-steps of 4)
 typedef double v4f64 __attribute__((ext_vector_type(4)));

@@ -80,7 +80,7 @@ __device__ __attribute__((noinline)) unsigned body_entry(const StreamArgs& a, in
   constexpr int CL = kBodyPanelLd;
   const int WL = 3 * M;
   const int tid = threadIdx.x, n = a.n;
-  const DevParams& prm = *a.dp;
+  const DevParams& prm = a.prm(uniform_filter(b));
   const BodyLds lds(a.nxs, n, M);
   double* xs = smem + lds.xs;
   double* lam = smem + lds.lam;
@@ -246,7 +246,7 @@ __global__ __launch_bounds__(T, 3) void k_update_body_n(StreamArgs a, int M, uns
   const int b = blockIdx.x, tid = threadIdx.x;
   if (b >= a.B) return;
   const int n = a.n, ld = a.ld;
-  const DevParams& prm = *a.dp;
+  const DevParams& prm = a.prm(b);
   const BodyLds lds(a.nxs, n, M);
   double* xs = smem + lds.xs;
   double* lam = smem + lds.lam;
@@ -264,7 +264,7 @@ __global__ __launch_bounds__(T, 3) void k_update_body_n(StreamArgs a, int M, uns
 
   // ---- load: x, lambda, the panel (lower triangle only: row i of column c, or its mirror image), the rho diagonals ----
   for (int i = tid; i < nxa; i += T) xs[i] = xg[i];
-  for (int i = tid; i < n; i += T) lam[i] = a.lambda[i];
+  for (int i = tid; i < n; i += T) lam[i] = a.lam(b)[i];
   for (int i = tid; i < nact; i += T) {
 #pragma unroll
     for (int c = 0; c < kBodyCols; c++) Cp[CL * i + c] = (i >= c) ? P[i + (long)c * ld] : P[c + (long)i * ld];

@@ -34,7 +34,7 @@ __global__ __launch_bounds__(T) void k_update_depths(StreamArgs a, int M, int or
   const int b = blockIdx.x, tid = threadIdx.x;
   if (b >= a.B) return;
   const int n = a.n, ld = a.ld;
-  const DevParams& prm = *a.dp;
+  const DevParams& prm = a.prm(b);
   const DepthLds lds(a.nxs, n, M);
   const int nW = lds.nW;
   double* xs = smem + lds.xs;
@@ -53,7 +53,7 @@ __global__ __launch_bounds__(T) void k_update_depths(StreamArgs a, int M, int or
 
   // ---- load: x, lambda, the rho diagonals, and for every entry the column of the start P its slot names (lower triangle only:
   //      row i of column c, or its mirror image) -- all of the chain's global loads, issued together ----
-  onepass_load<T>(a, xg, P, len, xs, lam, D);
+  onepass_load<T>(a, b, xg, P, len, xs, lam, D);
   for (int i = tid; i < nact; i += T) {
     constexpr int UL = 8;   // columns a thread has in flight (the chain cannot start before the last of them is in)
     for (int e0 = 0; e0 < M; e0 += UL) {

@@ -240,7 +240,7 @@ __global__ __launch_bounds__(64) void k_diag_innovation(StreamArgs a, int type, 
     const double* R = R_all + (long)b * rsb + (long)mi * rsm;   // column-major rdim x rdim
     int cols[6], nc = 0;
     double Hc[18], zhat[4] = {0.0, 0.0, 0.0, 0.0}, W[6][3], Sr[9], Si[9];
-    meas_model(type, xs, slot, *a.dp, zhat, cols, Hc, nc);
+    meas_model(type, xs, slot, a.prm(b), zhat, cols, Hc, nc);
     r3[0] = r3[1] = r3[2] = 0.0;
     meas_residual(type, z, zhat, zdim, r3);
     for (int ci = 0; ci < nc; ci++) {                                  // W = P H^T at the rows H touches

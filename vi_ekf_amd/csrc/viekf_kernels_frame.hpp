@@ -188,7 +188,7 @@ __global__ __launch_bounds__(T) void k_init_features(StreamArgs a, const int* __
   const long bN = (long)b * a.N;
   for (int k = tid; k < cnt; k += T) {
     double q[4], rho;
-    init_feature_state(newpix + 2 * (bN + k), newdepth[bN + k], (*a.dp), q, &rho);
+    init_feature_state(newpix + 2 * (bN + k), newdepth[bN + k], a.prm(b), q, &rho);
     double* xf = a.x + a.si(b) * a.nxs + xZ + 5 * (len + k);
     xf[0] = q[0]; xf[1] = q[1]; xf[2] = q[2]; xf[3] = q[3]; xf[4] = rho;
   }
@@ -201,7 +201,7 @@ __global__ __launch_bounds__(T) void k_init_features(StreamArgs a, const int* __
     }
     if (tid < 9) {
       const int r = tid % 3, c = tid / 3;
-      P[(d0 + r) + (long)(d0 + c) * ld] = (r == c) ? a.dp->P0_feat[r] : 0.0;
+      P[(d0 + r) + (long)(d0 + c) * ld] = (r == c) ? a.prm(b).P0_feat[r] : 0.0;
     }
   }
   __syncthreads();

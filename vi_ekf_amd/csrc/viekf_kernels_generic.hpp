@@ -24,7 +24,7 @@ __global__ __launch_bounds__(T) void k_update_generic(StreamArgs a, int type, in
   const int b = blockIdx.x, tid = threadIdx.x;
   if (b >= a.B) return;
   const int n = a.n, ld = a.ld;
-  const DevParams& prm = *a.dp;
+  const DevParams& prm = a.prm(b);
   const GenLds lds(a.nxs, n);
   double* xs = smem + lds.xs;     // [nxs]
   double* W = smem + lds.W;       // [n][3]
@@ -48,7 +48,7 @@ __global__ __launch_bounds__(T) void k_update_generic(StreamArgs a, int type, in
     if (isnan_) { if (res_out && tid == 0) *res_out = 2; return; }   // MEAS_NAN
   }
   for (int i = tid; i < xZ + 5 * len; i += T) xs[i] = xg[i];
-  for (int i = tid; i < n; i += T) lam[i] = a.lambda[i];
+  for (int i = tid; i < n; i += T) lam[i] = a.lam(b)[i];
   __syncthreads();
 
   if (tid == 0) {   // measurement model: zhat, the non-zero columns of H, residual

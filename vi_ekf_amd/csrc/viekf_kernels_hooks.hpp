@@ -36,10 +36,10 @@ __global__ __launch_bounds__(T) void k_eval_xdot(StreamArgs a, const double* __r
   __syncthreads();
   if (tid == 0) {
     double ub[6];
-    q_rota(a.dp->q_b_u, u_all + (long)b * 6, ub);          // vi_ekf.cpp:265-267
-    q_rota(a.dp->q_b_u, u_all + (long)b * 6 + 3, ub + 3);
-    body_ctx(xs, ub, (*a.dp), *ctx);
-    body_dynamics(*ctx, (*a.dp), xdb, Abb, Gb);
+    q_rota(a.prm(b).q_b_u, u_all + (long)b * 6, ub);          // vi_ekf.cpp:265-267
+    q_rota(a.prm(b).q_b_u, u_all + (long)b * 6 + 3, ub + 3);
+    body_ctx(xs, ub, a.prm(b), *ctx);
+    body_dynamics(*ctx, a.prm(b), xdb, Abb, Gb);
   }
   __syncthreads();
   double* o = out + (long)b * a.n;
@@ -64,7 +64,7 @@ __global__ void k_eval_h(StreamArgs a, int type, const int* __restrict__ slot_al
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= a.B) return;
   const double* xs = a.x + a.si(b) * a.nxs;
-  const DevParams& prm = *a.dp;
+  const DevParams& prm = a.prm(b);
   const double nan = __longlong_as_double(0x7ff8000000000000LL);
   double zhat[4] = {nan, nan, nan, nan};
   const bool needs_slot = meas_needs_slot(type);
@@ -95,8 +95,8 @@ __global__ __launch_bounds__(256) void k_eval_jacobians(StreamArgs a, const doub
   if (G) for (int e = tid; e < n * 6; e += 256) G[e] = 0.0;
   if (xd) for (int e = tid; e < n; e += 256) xd[e] = 0.0;
   if (tid == 0) {
-    body_ctx(xs, u_all + (long)b * 6, *a.dp, ctx);
-    body_dynamics(ctx, *a.dp, xdb, Abb, Gb);                              // vi_ekf_dyn.cpp:42-80
+    body_ctx(xs, u_all + (long)b * 6, a.prm(b), ctx);
+    body_dynamics(ctx, a.prm(b), xdb, Abb, Gb);                              // vi_ekf_dyn.cpp:42-80
   }
   __syncthreads();
   for (int e = tid; e < 256; e += 256) { const int r = e >> 4, c = e & 15; if (A) A[r + (long)c * n] = Abb[e]; }
@@ -140,7 +140,7 @@ __global__ void k_eval_H(StreamArgs a, const double* __restrict__ x_in, int type
   }
   int cols[6], nc = 0;
   double Hc[18];
-  meas_model(type, xs, slot, *a.dp, zhat, cols, Hc, nc);
+  meas_model(type, xs, slot, a.prm(b), zhat, cols, Hc, nc);
   for (int c = 0; c < nc; c++)
     for (int r = 0; r < 3; r++) H[r + 3L * cols[c]] = Hc[r * 6 + c];
   for (int i = 0; i < 4; i++) zhat_out[(long)b * 4 + i] = zhat[i];

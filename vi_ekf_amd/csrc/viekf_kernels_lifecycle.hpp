@@ -24,7 +24,7 @@ __global__ __launch_bounds__(T) void k_init_feature(StreamArgs a, const double* 
   const int d0 = 16 + 3 * len, dmax = d0 + 3;
   if (tid == 0) {
     double q[4], rho;
-    init_feature_state(pix_all + 2L * b, depth_all ? depth_all[b] : NAN, (*a.dp), q, &rho);
+    init_feature_state(pix_all + 2L * b, depth_all ? depth_all[b] : NAN, a.prm(b), q, &rho);
     double* xf = a.x + a.si(b) * a.nxs + xZ + 5 * len;
     xf[0] = q[0]; xf[1] = q[1]; xf[2] = q[2]; xf[3] = q[3]; xf[4] = rho;
   }
@@ -36,7 +36,7 @@ __global__ __launch_bounds__(T) void k_init_feature(StreamArgs a, const double* 
   }
   if (tid < 9) {
     const int r = tid % 3, c = tid / 3;
-    P[(d0 + r) + (long)(d0 + c) * ld] = (r == c) ? a.dp->P0_feat[r] : 0.0;
+    P[(d0 + r) + (long)(d0 + c) * ld] = (r == c) ? a.prm(b).P0_feat[r] : 0.0;
   }
   (void)dmax;
   __syncthreads();
@@ -161,9 +161,12 @@ __global__ __launch_bounds__(T) void k_keyframe_reset(StreamArgs a, const unsign
 }
 
 // fill every filter with the initial state (vi_ekf.cpp:70-81 / :134-144)
-__global__ void k_reset(StreamArgs a, const double* __restrict__ x0 /*17*/, const double* __restrict__ Pdiag /*n*/) {
+// x0 / Pdiag: one set (strides 0) or filter b's own at b * stride
+__global__ void k_reset(StreamArgs a, const double* __restrict__ x0 /*17*/, const double* __restrict__ Pdiag /*n*/, long x0_stride,
+                        long pd_stride) {
   const int b = blockIdx.x;
   if (b >= a.B) return;
+  x0 += b * x0_stride; Pdiag += b * pd_stride;
   double* xg = a.x + a.si(b) * a.nxs;
   double* P = a.P + a.si(b) * a.n * a.ld;
   for (int i = threadIdx.x; i < a.nxs; i += blockDim.x) xg[i] = (i < 17) ? x0[i] : 0.0;

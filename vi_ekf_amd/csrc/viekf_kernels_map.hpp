@@ -63,7 +63,7 @@ __device__ __forceinline__ void mp_shared(const StreamArgs& a, const double* __r
 __device__ __forceinline__ bool mp_landmark(const StreamArgs& a, const double* sh, int b, int j, int len, double (&l)[3], double (&S)[6]) {
   const double* xs = a.x + a.si(b) * a.nxs;
   const double* P = a.P + a.si(b) * a.n * a.ld;
-  const DevParams& dp = *a.dp;
+  const DevParams& dp = a.prm(b);
   const int r = dxZ + 3 * j;
   const long ld = a.ld;
   double pf[18], pd[6], xf[5];

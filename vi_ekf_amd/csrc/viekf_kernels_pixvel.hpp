@@ -78,7 +78,7 @@ __global__ __launch_bounds__(T) void k_update_pixvel(StreamArgs a, int M, int m,
   const int b = blockIdx.x, tid = threadIdx.x;
   if (b >= a.B) return;
   const int n = a.n, ld = a.ld;
-  const DevParams& prm = *a.dp;
+  const DevParams& prm = a.prm(b);
   const PixvelLds lds(a.nxs, n);
   double* xs = smem + lds.xs;
   double* W = smem + lds.W;
@@ -103,7 +103,7 @@ __global__ __launch_bounds__(T) void k_update_pixvel(StreamArgs a, int M, int m,
   }
   unsigned flag = 0;
   for (int i = tid; i < xZ + 5 * len; i += T) xs[i] = xg[i];
-  for (int i = tid; i < n; i += T) lam[i] = a.lambda[i];
+  for (int i = tid; i < n; i += T) lam[i] = a.lam(b)[i];
   __syncthreads();
   if (act == 0) {   // :230 -- an inactive measurement only runs fix_depth
     for (int f = tid; f < len; f += T) fix_depth_one(xs, P, ld, f, prm, flag);
@@ -217,7 +217,7 @@ __global__ __launch_bounds__(T) void k_update_pixvels(StreamArgs a, int M, int o
   const int b = blockIdx.x, tid = threadIdx.x;
   if (b >= a.B) return;
   const int n = a.n, ld = a.ld;
-  const DevParams& prm = *a.dp;
+  const DevParams& prm = a.prm(b);
   const PixvelsLds lds(a.nxs, n, (n - 16) / 3, M);
   const int nW = lds.nW;
   double* xs = smem + lds.xs;
@@ -240,7 +240,7 @@ __global__ __launch_bounds__(T) void k_update_pixvels(StreamArgs a, int M, int o
   auto p_low = [&](int i, int c) { return (i >= c) ? P[i + (long)c * ld] : P[c + (long)i * ld]; };   // (the lower triangle only)
   const int bcol[6] = {dxVEL, dxVEL + 1, dxVEL + 2, dxB_G, dxB_G + 1, dxB_G + 2};
 
-  onepass_load<T>(a, xg, P, len, xs, lam, D);
+  onepass_load<T>(a, b, xg, P, len, xs, lam, D);
   for (int i = tid; i < nact; i += T) {
     double v[6];
 #pragma unroll
@@ -384,7 +384,7 @@ __global__ __launch_bounds__(64) void k_eval_pixel_vel(StreamArgs a, const int* 
   int cols[kPixvelCols];
   const double nan = __longlong_as_double(0x7ff8000000000000LL);
   if (ok) {
-    pixel_vel_model(xs, slot, gyro_all + 3L * b, *a.dp, zhat, Hc);
+    pixel_vel_model(xs, slot, gyro_all + 3L * b, a.prm(b), zhat, Hc);
     pixel_vel_cols(slot, cols);
   }
   zhat_out[2L * b] = ok ? zhat[0] : nan;

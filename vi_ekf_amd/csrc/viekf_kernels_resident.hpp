@@ -52,14 +52,14 @@ __device__ __forceinline__ void res_prologue(const StreamArgs& a, ResShared& S, 
   {
     const double* xg = a.x + S.si * a.nxs;
     for (int i = tid; i < a.nxs; i += T) S.xs[i] = (i < xZ + 5 * S.len) ? xg[i] : 0.0;
-    for (int i = tid; i < a.n; i += T) S.lam[i] = a.lambda[i];
+    for (int i = tid; i < a.n; i += T) S.lam[i] = a.lam(b)[i];
     for (int i = tid; i < 2 * a.N; i += T) { S.fixadd[i] = 0.0; S.fixset[i] = 0.0; }
     if (tid < 48) {
-      const double lk = a.lambda[tid & 15], lq = a.lambda[16 + (tid >> 4)];
-      S.Lbc[tid] = a.dp->use_partial_update ? (lk + lq - lq * lk) : 1.0;
+      const double lk = a.lam(b)[tid & 15], lq = a.lam(b)[16 + (tid >> 4)];
+      S.Lbc[tid] = a.prm(b).use_partial_update ? (lk + lq - lq * lk) : 1.0;
     }
     // launch constants of the propagate's barrier intervals (res_prop_setup, res_prop_body): read from LDS there, not from memory
-    if (BL && tid >= T - 22) { const int i = tid - (T - 22); S.sm[res_sm::SQRTQU + i] = (i < 6) ? a.dp->sqrtQu[i] : a.Qx[i - 6]; }
+    if (BL && tid >= T - 22) { const int i = tid - (T - 22); S.sm[res_sm::SQRTQU + i] = (i < 6) ? a.prm(b).sqrtQu[i] : a.qx(b)[i - 6]; }
     if (tid == 0) {   // dt, and the words that must read zero when the step starts (res_sm)
       constexpr unsigned long long zero = sm_zero_mask(res_sm::kWords);
       S.sm[res_sm::DT] = launch_prop(do_prop) ? dt_all[b] : 0.0;

@@ -63,10 +63,10 @@ __global__ __launch_bounds__(T) void k_propagate_stream(StreamArgs a, const doub
 
   if (tid == 0) {
     double ub[6];
-    q_rota(a.dp->q_b_u, u_all + (long)b * 6, ub);          // vi_ekf.cpp:265-267
-    q_rota(a.dp->q_b_u, u_all + (long)b * 6 + 3, ub + 3);
-    body_ctx(xs, ub, (*a.dp), *ctx);
-    body_dynamics(*ctx, (*a.dp), xdb, Abb, Gb);               // vi_ekf_dyn.cpp:42-80
+    q_rota(a.prm(b).q_b_u, u_all + (long)b * 6, ub);          // vi_ekf.cpp:265-267
+    q_rota(a.prm(b).q_b_u, u_all + (long)b * 6 + 3, ub + 3);
+    body_ctx(xs, ub, a.prm(b), *ctx);
+    body_dynamics(*ctx, a.prm(b), xdb, Abb, Gb);               // vi_ekf_dyn.cpp:42-80
   }
   __syncthreads();
 
@@ -179,7 +179,7 @@ __global__ __launch_bounds__(T) void k_propagate_stream(StreamArgs a, const doub
       xr[16 + k] = ph; yr[16 + k] = vt;
       if (k < 8) {
         const double g = (k < 6) ? gd[(16 + r) * 6 + k] : 0.0;
-        xr[32 + k] = (k < 6) ? g * a.dp->Qu[k] : 0.0;
+        xr[32 + k] = (k < 6) ? g * a.prm(b).Qu[k] : 0.0;
         yr[32 + k] = g;
       }
     }
@@ -201,9 +201,9 @@ __global__ __launch_bounds__(T) void k_propagate_stream(StreamArgs a, const doub
     double s = 0.0;
     for (int k = 0; k < 16; k++) s += T16[r * 16 + k] * Phibb[c * 16 + k];
     double g = 0.0;
-    for (int k = 0; k < 6; k++) g += Gdb[r * 6 + k] * a.dp->Qu[k] * Gdb[c * 6 + k];
+    for (int k = 0; k < 6; k++) g += Gdb[r * 6 + k] * a.prm(b).Qu[k] * Gdb[c * 6 + k];
     s = s + g;
-    if (r == c) s += a.Qx[r];
+    if (r == c) s += a.qx(b)[r];
     P[(e >> 4) + (long)(e & 15) * ld] = s;
   }
   // ---- body/feature cross blocks (the feature-row copy, mirrored)
@@ -212,7 +212,7 @@ __global__ __launch_bounds__(T) void k_propagate_stream(StreamArgs a, const doub
     double s = 0.0;
     for (int c = 0; c < 16; c++) s += U[r * 16 + c] * Phibb[k * 16 + c];
     double g = 0.0;
-    for (int q = 0; q < 6; q++) g += gd[(16 + r) * 6 + q] * a.dp->Qu[q] * Gdb[k * 6 + q];
+    for (int q = 0; q < 6; q++) g += gd[(16 + r) * 6 + q] * a.prm(b).Qu[q] * Gdb[k * 6 + q];
     P[(16 + r) + (long)k * ld] = s + g;
     if (!MF) P[k + (long)(16 + r) * ld] = s + g;   // (the matrix-core variant keeps the lower triangle only, see below)
   }
@@ -306,7 +306,7 @@ __global__ __launch_bounds__(T) void k_propagate_stream(StreamArgs a, const doub
             const int j = c0 + 16 * q + lk + 4 * rg;
             if (i < nact && j < nact && i >= j) {
               double v = O[q][aa][rg];
-              if (i == j) v += a.Qx[i];
+              if (i == j) v += a.qx(b)[i];
               P[i + (long)j * ld] = v;
             }
           }
@@ -334,9 +334,9 @@ __global__ __launch_bounds__(T) void k_propagate_stream(StreamArgs a, const doub
           for (int k = 0; k < 16; k++) s += U[(3 * I + r) * 16 + k] * phi_fb[(3 * J + c) * 16 + k];
           for (int m = 0; m < 3; m++) s += Mij[r * 3 + m] * phi_ff[9 * J + c * 3 + m];
           double g = 0.0;
-          for (int q = 0; q < 6; q++) g += gd[(r0 + r) * 6 + q] * a.dp->Qu[q] * gd[(c0 + c) * 6 + q];
+          for (int q = 0; q < 6; q++) g += gd[(r0 + r) * 6 + q] * a.prm(b).Qu[q] * gd[(c0 + c) * 6 + q];
           s = s + g;
-          if (I == J && r == c) s += a.Qx[r0 + r];
+          if (I == J && r == c) s += a.qx(b)[r0 + r];
           out[r * 3 + c] = s;
         }
       if (I == J) { out[1] = out[3]; out[2] = out[6]; out[5] = out[7]; }   // diagonal block: upper <- lower
@@ -348,12 +348,12 @@ __global__ __launch_bounds__(T) void k_propagate_stream(StreamArgs a, const doub
     }
   }
   // inactive slots: Phi = I and G = 0 there, so only Qx is added (vi_ekf.cpp:139-144,304)
-  for (int d = nact + tid; d < n; d += T) P[d + (long)d * ld] += a.Qx[d];
+  for (int d = nact + tid; d < n; d += T) P[d + (long)d * ld] += a.qx(b)[d];
   __syncthreads();
 
   // ---- fix_depth (vi_ekf.cpp:311) and write the state back
   unsigned flag = 0;
-  for (int i = tid; i < len; i += T) fix_depth_one(xs, P, ld, i, (*a.dp), flag);
+  for (int i = tid; i < len; i += T) fix_depth_one(xs, P, ld, i, a.prm(b), flag);
   __syncthreads();
   for (int i = tid; i < xZ + 5 * len; i += T) {
     const double v = xs[i];
@@ -392,7 +392,7 @@ __global__ __launch_bounds__(T) void k_update_feat_stream(StreamArgs a, const do
   unsigned flag = 0;
 
   for (int i = tid; i < xZ + 5 * len; i += T) xs[i] = xg[i];
-  for (int i = tid; i < n; i += T) lam[i] = a.lambda[i];
+  for (int i = tid; i < n; i += T) lam[i] = a.lam(b)[i];
   __syncthreads();
 
   for (int m = 0; m < M; m++) {
@@ -407,7 +407,7 @@ __global__ __launch_bounds__(T) void k_update_feat_stream(StreamArgs a, const do
     const int j0 = 16 + 3 * slot;
     if (tid == 0) {
       double zhat[2], Hb[4];
-      h_feat(xs + xZ + 5 * slot, (*a.dp), zhat, Hb);
+      h_feat(xs + xZ + 5 * slot, a.prm(b), zhat, Hb);
       sm[0] = zhat[0]; sm[1] = zhat[1];
       sm[2] = Hb[0]; sm[3] = Hb[1]; sm[4] = Hb[2]; sm[5] = Hb[3];
       sm[6] = z0 - zhat[0]; sm[7] = z1 - zhat[1];      // residual (vi_ekf_meas.cpp:220)
@@ -449,7 +449,7 @@ __global__ __launch_bounds__(T) void k_update_feat_stream(StreamArgs a, const do
     if (h00 != h00 || h01 != h01 || h10 != h10 || h11 != h11) bad = 1;
     bad = __syncthreads_or(bad);
     if (!bad) {
-      const bool partial = a.dp->use_partial_update != 0;
+      const bool partial = a.prm(b).use_partial_update != 0;
       // state correction  x <- x [+] (lambda o K r)   (:254-255 / :262-263)
       if (tid == 0) {
         double dxb[16], xo[17];
@@ -488,7 +488,7 @@ __global__ __launch_bounds__(T) void k_update_feat_stream(StreamArgs a, const do
       }
     }
     __syncthreads();
-    for (int f = tid; f < len; f += T) fix_depth_one(xs, P, ld, f, (*a.dp), flag);   // :271
+    for (int f = tid; f < len; f += T) fix_depth_one(xs, P, ld, f, a.prm(b), flag);   // :271
     if (res && tid == 0) *res = 0;
     __syncthreads();
   }
@@ -667,14 +667,14 @@ __global__ __launch_bounds__(T) void k_update_feat_blocked(StreamArgs a, const d
   double* P = a.P + a.si(b) * n * ld;
   const int len = a.len[b];
   const int nact = 16 + 3 * len;
-  const DevParams& prm = *a.dp;
+  const DevParams& prm = a.prm(b);
   const bool partial = prm.use_partial_update != 0;
   unsigned flag = 0;
   constexpr int NWV = T / 64;
   const int lane = tid & 63, wave = tid >> 6;
 
   for (int i = tid; i < xZ + 5 * len; i += T) xs[i] = xg[i];
-  for (int i = tid; i < n; i += T) lam[i] = a.lambda[i];
+  for (int i = tid; i < n; i += T) lam[i] = a.lam(b)[i];
   __syncthreads();
 
   int m = 0, mbase = 0;

@@ -45,7 +45,7 @@ __global__ __launch_bounds__(T) void k_propagate_wide(StreamArgs a, const double
   BodyCtx* ctx = reinterpret_cast<BodyCtx*>(smem + L.ctx);
   double* AvG = smem + L.AvG; double* PsiP = smem + L.PsiP; double* Pi = smem + L.Pi; double* Xi = smem + L.Xi;
   double* phiff = smem + L.phiff; double* Z = smem + L.Z;
-  const DevParams& prm = *a.dp;
+  const DevParams& prm = a.prm(b);
 
   double* xg = a.x + a.si(b) * a.nxs;
   double* P = a.P + a.si(b) * n * ld;
@@ -59,7 +59,7 @@ __global__ __launch_bounds__(T) void k_propagate_wide(StreamArgs a, const double
   for (int i = tid; i < 96; i += T) Gb[i] = 0.0;
   if (tid < 16) xdb[tid] = 0.0;
   __syncthreads();
-  if (tid == 0) res_body_phase(xs, u_all + (long)b * 6, a.dp, ctx, xdb, Abb, Gb);   // vi_ekf_dyn.cpp:42-80 (rotates u by q_b_u)
+  if (tid == 0) res_body_phase(xs, u_all + (long)b * 6, &a.prm(b), ctx, xdb, Abb, Gb);   // vi_ekf_dyn.cpp:42-80 (rotates u by q_b_u)
   __syncthreads();
   // ---- feature dynamics: raw Jacobian blocks -> the even record slots, Phi_ff, state step (one lane per feature);
   //      A_v G_b for the row expansion on lanes that carry no feature
@@ -212,7 +212,7 @@ __global__ __launch_bounds__(T) void k_propagate_wide(StreamArgs a, const double
 #pragma unroll
     for (int k = 0; k < 6; k++) g += Gdb[r * 6 + k] * Gdb[c * 6 + k];
     s += g;
-    if (r == c) s += a.Qx[r];
+    if (r == c) s += a.qx(b)[r];
     P[(e >> 4) + (long)(e & 15) * ld] = s;
   }
   __syncthreads();   // the records are complete
@@ -299,7 +299,7 @@ __global__ __launch_bounds__(T) void k_propagate_wide(StreamArgs a, const double
             const int j = c0 + 16 * q + lk + 4 * rg;
             if (i < nact && j < nact && i >= j) {
               double v = O[q][aa][rg];
-              if (i == j) v += a.Qx[i];
+              if (i == j) v += a.qx(b)[i];
               P[i + (long)j * ld] = v;
             }
           }
@@ -307,7 +307,7 @@ __global__ __launch_bounds__(T) void k_propagate_wide(StreamArgs a, const double
     }
   }
   // inactive slots: Phi = I and G = 0 there, so only Qx is added (vi_ekf.cpp:139-144,304)
-  for (int d = nact + tid; d < n; d += T) P[d + (long)d * ld] += a.Qx[d];
+  for (int d = nact + tid; d < n; d += T) P[d + (long)d * ld] += a.qx(b)[d];
   __syncthreads();
 
   // ---- fix_depth (vi_ekf.cpp:311) and write the state back
@@ -619,7 +619,7 @@ __global__ __launch_bounds__(T) void k_update_feat_panelsvc(StreamArgs a, const 
   double* P = a.P + a.si(b) * n * ld;
   const int len = a.len[b];
   const int nact = 16 + 3 * len;
-  const DevParams& prm = *a.dp;
+  const DevParams& prm = a.prm(b);
   const bool partial = prm.use_partial_update != 0;
   unsigned flag = 0;
   const int lane = tid & 63, wave = tid >> 6;
@@ -630,7 +630,7 @@ __global__ __launch_bounds__(T) void k_update_feat_panelsvc(StreamArgs a, const 
 #endif
 
   for (int i = tid; i < xZ + 5 * len; i += T) xs[i] = xg[i];
-  for (int i = tid; i < n; i += T) lam[i] = a.lambda[i];
+  for (int i = tid; i < n; i += T) lam[i] = a.lam(b)[i];
   for (int f = tid; f < len; f += T) diag[f] = P[(16 + 3 * f + 2) + (long)(16 + 3 * f + 2) * ld];
   for (int i = nact * BLD + tid; i < ((n + 15) & ~15) * BLD; i += T) Wp[i] = 0.0;   // the panel rows past the active ones stay zero (psv_pass)
   __syncthreads();

@@ -82,11 +82,11 @@ __device__ __forceinline__ double onepass_rebuild(double v, double L, const doub
 
 // The prologue's loads: x, lambda and the rho diagonals.
 template <int T>
-__device__ __forceinline__ void onepass_load(const StreamArgs& a, const double* xg, const double* P, int len, double* xs, double* lam,
+__device__ __forceinline__ void onepass_load(const StreamArgs& a, int b, const double* xg, const double* P, int len, double* xs, double* lam,
                                              double* D) {
   const int tid = threadIdx.x, ld = a.ld;
   for (int i = tid; i < xZ + 5 * len; i += T) xs[i] = xg[i];
-  for (int i = tid; i < a.n; i += T) lam[i] = a.lambda[i];
+  for (int i = tid; i < a.n; i += T) lam[i] = a.lam(b)[i];
   for (int f = tid; f < len; f += T) { const long dR = dxZ + 3 * f + 2; D[f] = P[dR + dR * ld]; }
 }
 

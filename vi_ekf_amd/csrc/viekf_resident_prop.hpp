@@ -144,7 +144,7 @@ __device__ __forceinline__ int res_clamp3(int v) { return min(max(v, 0), 2); }
 // ahead of the workers' Ut product.  LDSC: sqrt(Qu) from the LDS copy (see res_prop_setup).
 template <bool LDSC>
 __device__ __forceinline__ void res_prop_setup_body_service(const StreamArgs& a, const ResShared& S, int lane, double dt) {
-  const DevParams& prm = *a.dp;
+  const DevParams& prm = a.prm(uniform_filter(S.b));
   {   // (a)  items 0..3: Phi_bb / M_bb element lane + 64 j;  4..6: Psi P_bb element lane + 64 (j - 4) < 144
     const double* x[7]; const double* y[7];
     const int ys[7] = {16, 16, 16, 16, 16, 16, 16};
@@ -255,7 +255,7 @@ struct ResNoHook { template <class K> __device__ __forceinline__ void operator()
 template <int TW, bool LDSC = false, class Hook = ResNoHook, bool SS = false>
 __device__ __forceinline__ void res_prop_setup(const StreamArgs& a, const ResShared& S, int tid, const Hook& hook = Hook()) {
   const int nf = S.nf, N = S.N;
-  const DevParams& prm = *a.dp;
+  const DevParams& prm = a.prm(uniform_filter(S.b));
   double* Pbc = S.Pbc; double* Pbb = S.Pbb;
   double* Z = S.Z; double* phiff = S.phiff;
   double* Phibb = S.Phibb; double* Mbb = S.Mbb; double* Gdb = S.Gdb; double* T16 = S.T16;
@@ -394,7 +394,7 @@ __device__ __forceinline__ void res_prop_setup(const StreamArgs& a, const ResSha
 // P+[feature rows, body columns] = V Phi_bb^T + D Xi + Gs Gs_b^T, in LDS and in place (a tile's rows are read before they are
 // written, by the same wave), and the body block (-> Mbb).  (nf x 16)(16 x 16) + (nf x 16)(16 x 16) on the matrix cores, one
 // 16-row tile per wave and turn, 4 + 4 k-steps: the second product's k runs over D[0..8], Gs[0..5] and one zero.
-// LDSC: Qx of the 16 body rows from the resident family's LDS copy (res_sm::QXB: see res_prop_setup), else a.Qx.
+// LDSC: Qx of the 16 body rows from the resident family's LDS copy (res_sm::QXB: see res_prop_setup), else StreamArgs::qx.
 template <int TW, bool LDSC = false>
 __device__ __forceinline__ void res_prop_body(const StreamArgs& a, const ResShared& S, int tid) {
   const int nf = S.nf;
@@ -458,7 +458,7 @@ __device__ __forceinline__ void res_prop_body(const StreamArgs& a, const ResShar
 #pragma unroll
     for (int r4 = 0; r4 < 4; r4++) {
       const int r = lk + 4 * r4, c = lr;                           // a result lane holds column lr of rows lk + 4 r4
-      S.Mbb[r * 16 + c] = acc[r4] + ((r == c) ? (LDSC ? S.sm[res_sm::QXB + r] : a.Qx[r]) : 0.0); // P_bb+ staged in Mbb (T16 / Pbb are still being read)
+      S.Mbb[r * 16 + c] = acc[r4] + ((r == c) ? (LDSC ? S.sm[res_sm::QXB + r] : a.qx(uniform_filter(S.b))[r]) : 0.0); // P_bb+ staged in Mbb (T16 / Pbb are still being read)
     }
   }
 }

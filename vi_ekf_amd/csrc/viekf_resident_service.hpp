@@ -19,7 +19,7 @@ __device__ __forceinline__ void res_service(const StreamArgs& a, const ResShared
                                             const double* __restrict__ u_all, const double* __restrict__ dt_all,
                                             int* __restrict__ result_all) {
   const int N = S.N, n = S.n, len = S.len, M = S.M;
-  const DevParams& prm = *a.dp;
+  const DevParams& prm = a.prm(uniform_filter(S.b));
   double* xs = S.xs;
   double* sm = S.sm;
   unsigned flag = 0;
@@ -38,7 +38,7 @@ __device__ __forceinline__ void res_service(const StreamArgs& a, const ResShared
     for (int i = lane; i < 256; i += 64) S.Abb[i] = 0.0;
     for (int i = lane; i < 96; i += 64) S.Gb[i] = 0.0;
     if (lane < 16) S.xdb[lane] = 0.0;
-    if (lane == 0) res_body_phase(xs, u_all + ((long)kp * S.B + S.b) * 6, a.dp, S.ctx, S.xdb, S.Abb, S.Gb);
+    if (lane == 0) res_body_phase(xs, u_all + ((long)kp * S.B + S.b) * 6, &prm, S.ctx, S.xdb, S.Abb, S.Gb);
     RES_STAMP(S, lane == 0 && kp == 0, 2);
     // (same wave: the LDS accesses of lane 0 above are complete before the other lanes read ctx / A_bb / G_b)
     wave_lds_sync();
@@ -80,7 +80,7 @@ __device__ __forceinline__ void res_service(const StreamArgs& a, const ResShared
     }
     if (PRIMARY && lane == 0) sm[res_sm::fix_word(ROLE, par)] = 0.0;
     for (int f = lane; PRIMARY && f < len; f += 64)   // fix_depth (vi_ekf.cpp:311): state here, covariance through the mailbox
-      res_fix_depth(xs + xZ + 5 * f, a.dp, &S.fixadd[par * N + f], &S.fixset[par * N + f], &sm[res_sm::fix_word(ROLE, par)], &flag);
+      res_fix_depth(xs + xZ + 5 * f, &prm, &S.fixadd[par * N + f], &S.fixset[par * N + f], &sm[res_sm::fix_word(ROLE, par)], &flag);
     par ^= 1;
     RES_STAMP(S, lane == 0, 6);
     if (SS) {
@@ -140,7 +140,7 @@ __device__ __forceinline__ void res_service(const StreamArgs& a, const ResShared
   // (wave-uniform constants of the update loop are forced into SGPRs: as VGPR pairs they were a fifth of the loop's live set)
   const double rho_reset = uniform_f64(1.0 / (2.0 * prm.min_depth));
   // Lambda of the zeta-zeta 2x2 block (lambda_feat[0], lambda_feat[1])
-  const double lz0 = uniform_f64(a.lambda[16]), lz1 = uniform_f64(a.lambda[17]);
+  const double lz0 = uniform_f64(a.lam(uniform_filter(S.b))[16]), lz1 = uniform_f64(a.lam(uniform_filter(S.b))[17]);
   const double L00 = uniform_f64(partial ? (lz0 + lz0 - lz0 * lz0) : 1.0), L01 = uniform_f64(partial ? (lz0 + lz1 - lz0 * lz1) : 1.0),
                L11 = uniform_f64(partial ? (lz1 + lz1 - lz1 * lz1) : 1.0);
 
@@ -222,7 +222,7 @@ __device__ __forceinline__ void res_service(const StreamArgs& a, const ResShared
   // k3), with the workers' expression  p - Lambda (K . W):  feature rows i take K_i (own) and W of the column's feature,
   // body rows k take K of the column's feature and W_k, as the block sweep and the body-column sweep do.  Everything this
   // needs is complete at the top of a phase, so it runs there, off the critical path.
-  const double lfz[3] = {lz0, lz1, uniform_f64(a.lambda[18])};
+  const double lfz[3] = {lz0, lz1, uniform_f64(a.lam(uniform_filter(S.b))[18])};
   // The dot products are  K_i . W_j  for a feature row i (own K row, the column feature's W row -- uniform over the lanes) and
   // K_j . W_k  for a body row k (the column feature's K row -- uniform --, own W row): one form  own . uni  with the lane's own
   // operand kept from gain_rows (Rows::oX) and the uniform one read out of the registers of the column feature's lane (single

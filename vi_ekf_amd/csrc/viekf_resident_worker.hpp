@@ -144,7 +144,7 @@ __device__ __forceinline__ void res_worker(const StreamArgs& a, const ResShared&
   // diagonal block (t, t).
   const int tid_ = tid;
   constexpr int NWV = TW / 64;
-  const DevParams& prm = *a.dp;
+  const DevParams& prm = a.prm(uniform_filter(S.b));
   double* Pbc = S.Pbc;   // [nf][16]  P[16+row][k]: the body columns of P live in LDS for the whole step
   double* Pbb = S.Pbb;   // [16][16]  row-major P_bb
   // (P[body rows, feature cols] is NOT kept: P is symmetric up to rounding, the mirror is written at store time)
@@ -171,7 +171,7 @@ __device__ __forceinline__ void res_worker(const StreamArgs& a, const ResShared&
   double Lff[9];
   bool partial_su = false;
   if (SU) {
-    const double lf[3] = {a.lambda[16], a.lambda[17], a.lambda[18]};
+    const double lf[3] = {a.lam(uniform_filter(S.b))[16], a.lam(uniform_filter(S.b))[17], a.lam(uniform_filter(S.b))[18]};
 #pragma unroll
     for (int r = 0; r < 3; r++)
 #pragma unroll
@@ -209,7 +209,7 @@ __device__ __forceinline__ void res_worker(const StreamArgs& a, const ResShared&
       for (int ia = 0; ia < RB; ia++) ws[ia] = ew[ia];
       if (S.do_prop) {
 #pragma unroll
-        for (int r = 0; r < 3; r++) qs[r] = a.Qx[16 + 3 * min(tq, N - 1) + r];
+        for (int r = 0; r < 3; r++) qs[r] = a.qx(uniform_filter(S.b))[16 + 3 * min(tq, N - 1) + r];
       }
     }
 #pragma unroll
@@ -284,7 +284,7 @@ __device__ __forceinline__ void res_worker(const StreamArgs& a, const ResShared&
   // (SU: a use of the blocks -- it follows B3p, or the propagate section of a launch without a propagate)
   if (!SU) {
     sym_diag();
-    const double lf[3] = {a.lambda[16], a.lambda[17], a.lambda[18]};
+    const double lf[3] = {a.lam(uniform_filter(S.b))[16], a.lam(uniform_filter(S.b))[17], a.lam(uniform_filter(S.b))[18]};
 #pragma unroll
     for (int r = 0; r < 3; r++)
 #pragma unroll
@@ -327,7 +327,7 @@ __device__ __forceinline__ void res_worker(const StreamArgs& a, const ResShared&
       const int tq = opaque(tid_);
       res_words<RB, TW>(resmap, tq, ep);
 #pragma unroll
-      for (int r = 0; r < 3; r++) qd[r] = a.Qx[16 + 3 * min(tq, N - 1) + r];
+      for (int r = 0; r < 3; r++) qd[r] = a.qx(uniform_filter(S.b))[16 + 3 * min(tq, N - 1) + r];
     }
     // (multi-propagate instances: sqrt(Qu) stays a memory operand of the set-up -- cached after the first propagate; the LDS
     //  operand cost them 16 .. 22 scalar-register reloads per update in the service loop)
@@ -367,9 +367,9 @@ __device__ __forceinline__ void res_worker(const StreamArgs& a, const ResShared&
       if (BL) {
         if (ia == 0 && own_diag) { pb[0][0] += qd[0]; pb[0][4] += qd[1]; pb[0][8] += qd[2]; }   // (the only diagonal blocks)
       } else if (v && I == J) {
-        pb[ia][0] += a.Qx[16 + 3 * I + 0];
-        pb[ia][4] += a.Qx[16 + 3 * I + 1];
-        pb[ia][8] += a.Qx[16 + 3 * I + 2];
+        pb[ia][0] += a.qx(uniform_filter(S.b))[16 + 3 * I + 0];
+        pb[ia][4] += a.qx(uniform_filter(S.b))[16 + 3 * I + 1];
+        pb[ia][8] += a.qx(uniform_filter(S.b))[16 + 3 * I + 2];
       }
       __builtin_amdgcn_sched_barrier(0);
       if (RB > 4) {   // pin the block's new values here: their arithmetic is otherwise sunk towards its first use, with the

@@ -20,6 +20,9 @@
 
 #include "../../include/viekf.h"
 
+// (see cache_params)
+extern "C" int viekf_batch_get_params_filter(const viekf_batch* b, int32_t filter, viekf_params* out) __attribute__((weak));
+
 #ifdef VIEKF_SEQ_TRACE
 #include <cstdio>
 #define TR(...) std::fprintf(stderr, __VA_ARGS__)
@@ -152,7 +155,8 @@ struct viekf_seq {
   bool indep = false;                                              // independent clocks
   std::vector<FilterSeq> fs;
   int B = 0, N = 0, H = 0, MH = 0;
-  viekf_params prm;
+  viekf_params prm;                 // the core's creation set: the structural fields (one value per batch)
+  std::vector<viekf_params> fprm;   // [B] every filter's set as the core had it when the sequencer was created (cache_params)
   std::vector<double> t;                                           // t_ ring
   std::vector<uint8_t> mat;                                        // ring slot holds its state (0: a step inside a fused replay --
                                                                    // its time is known, its state is re-created on demand)
@@ -284,8 +288,8 @@ int propagate_core(viekf_seq* s, const double* u, double t, bool save_input) {
   if (save_input) {
     std::vector<double> ub((size_t)B * 6);
     for (int b = 0; b < B; b++) {
-      rota(s->prm.q_b_u, u + 6 * b, ub.data() + 6 * b);
-      rota(s->prm.q_b_u, u + 6 * b + 3, ub.data() + 6 * b + 3);
+      rota(s->fprm[b].q_b_u, u + 6 * b, ub.data() + 6 * b);
+      rota(s->fprm[b].q_b_u, u + 6 * b + 3, ub.data() + 6 * b + 3);
     }
     s->u.emplace_front(t, std::move(ub));                          // :269-272 (the ROTATED input is stored)
   }
@@ -519,8 +523,8 @@ bool plan_propagate(viekf_seq* s, int b, const double* u_in, double t, bool save
   if (save_input) {
     FInput in;
     in.t = t;
-    rota(s->prm.q_b_u, u_in, in.u);
-    rota(s->prm.q_b_u, u_in + 3, in.u + 3);
+    rota(s->fprm[b].q_b_u, u_in, in.u);
+    rota(s->fprm[b].q_b_u, u_in + 3, in.u + 3);
     f.u.push_front(in);                                            // :269-272 (the ROTATED input is stored)
   }
   if (std::isnan(f.start_t)) { f.start_t = t; f.t[f.i] = t; return false; }   // :274-279
@@ -772,6 +776,17 @@ int run_ops(viekf_seq* s, std::vector<std::vector<SeqOp>>& ops, std::vector<std:
   return VIEKF_OK;
 }
 
+// The core's creation set and every filter's own.  The per-filter getter is an additive entry point of the batch ABI: a provider
+// of the batch calls that lacks it (the symbol is weak here) has one set, which every filter then gets.
+int cache_params(viekf_seq* s, viekf_batch* core, int B) {
+  if (int rc = viekf_batch_get_params(core, &s->prm)) return rc;
+  s->fprm.assign((size_t)B, s->prm);
+  if (viekf_batch_get_params_filter)
+    for (int b = 0; b < B; b++)
+      if (int rc = viekf_batch_get_params_filter(core, b, &s->fprm[(size_t)b])) return rc;
+  return VIEKF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -782,7 +797,7 @@ int viekf_seq_create(viekf_batch* core, int32_t state_hist, int32_t meas_hist, v
   s->core = core;
   int32_t B, N, nx, n;
   if (int rc = viekf_batch_dims(core, &B, &N, &nx, &n)) { delete s; return rc; }
-  if (int rc = viekf_batch_get_params(core, &s->prm)) { delete s; return rc; }
+  if (int rc = cache_params(s, core, B)) { delete s; return rc; }
   if (int rc = viekf_batch_history_resize(core, state_hist + 1)) { delete s; return rc; }   // (+ 1: the buffer outside the ring)
   if (int rc = viekf_batch_snapshot(core, 0)) { delete s; return rc; }     // the live state moves into ring slot i_ = 0
   if (int rc = viekf_batch_select(core, 0)) { delete s; return rc; }
@@ -823,7 +838,7 @@ int viekf_seq_create_independent(viekf_batch* core, int32_t state_hist, int32_t 
   s->indep = true;
   int32_t B, N, nx, n;
   if (int rc = viekf_batch_dims(core, &B, &N, &nx, &n)) { delete s; return rc; }
-  if (int rc = viekf_batch_get_params(core, &s->prm)) { delete s; return rc; }
+  if (int rc = cache_params(s, core, B)) { delete s; return rc; }
   if (int rc = viekf_batch_history_resize(core, state_hist)) { delete s; return rc; }
   s->B = B; s->N = N; s->H = state_hist; s->MH = meas_hist;
   s->fs.resize(B);
@@ -1397,8 +1412,8 @@ int viekf_seq_get_feat(viekf_seq* s, const int32_t* id, double* pix, double* dep
       const double* f = x.data() + (size_t)b * nx + 17 + 5 * i;
       double z[3];
       rota(f, ez, z);
-      px[0] = s->prm.focal_len[0] * z[0] / z[2] + s->prm.cam_center[0];
-      px[1] = s->prm.focal_len[1] * z[1] / z[2] + s->prm.cam_center[1];
+      px[0] = s->fprm[b].focal_len[0] * z[0] / z[2] + s->fprm[b].cam_center[0];
+      px[1] = s->fprm[b].focal_len[1] * z[1] / z[2] + s->fprm[b].cam_center[1];
       d = 1.0 / f[4];
     }
     if (pix) { pix[2 * (size_t)b] = px[0]; pix[2 * (size_t)b + 1] = px[1]; }
@@ -1454,7 +1469,7 @@ int viekf_seq_init_logger(viekf_seq* s, const char* root_filename, const char* e
   std::vector<double> x, Pd;
   if (int rc = fetch_state_and_diag(s, x, Pd)) { s->log.clear(); return rc; }
   const int nx = 17 + 5 * s->N, n = 16 + 3 * s->N;
-  const viekf_params& p = s->prm;
+  const viekf_params& p = s->fprm[(size_t)filter];                 // (the recorded filter's own set)
   std::ofstream& c = s->log[LOG_CONF];                              // :100-116, line for line
   c << "Test Num: " << root_filename << "\n";
   c << "x0" << eigen_row(x.data() + (size_t)filter * nx, 17) << "\n";

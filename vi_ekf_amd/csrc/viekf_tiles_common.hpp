@@ -71,7 +71,7 @@ __device__ __forceinline__ void tile_prologue(const StreamArgs& a, TileShared& S
   if (present) {
     const double* xg = a.x + S.si * a.nxs;
     for (int i = tid; i < a.nxs; i += T) S.xs[i] = (i < xZ + 5 * S.len) ? xg[i] : 0.0;
-    for (int i = tid; i < a.n; i += T) S.lam[i] = a.lambda[i];
+    for (int i = tid; i < a.n; i += T) S.lam[i] = a.lam(uniform_filter(b))[i];
     for (int i = tid; i < 2 * a.N; i += T) { S.fixadd[i] = 0.0; S.fixset[i] = 0.0; }
     for (int i = tid; i < tile_sm::len(); i += T) S.sm[i] = (i == tile_sm::DT && launch_prop(do_prop)) ? dt_all[b] : 0.0;   // (all of it: tile_sm)
     for (int mm_ = tid; mm_ < M; mm_ += T) {

@@ -15,7 +15,7 @@ template <int T, bool MP, bool PAIR = false>
 __device__ __forceinline__ void tile_service(const StreamArgs& a, const TileShared& S, int lane, const double* __restrict__ u_all,
                                              const double* __restrict__ dt_all, int* __restrict__ result_all, int half = 0, int trips = 0) {
   const int N = S.N, len = S.len, M = S.M, NQ = S.NQ;
-  const DevParams& prm = *a.dp;
+  const DevParams& prm = a.prm(uniform_filter(S.b));
   double* xs = S.xs;
   double* sm = S.sm;
   unsigned flag = 0;
@@ -30,7 +30,7 @@ __device__ __forceinline__ void tile_service(const StreamArgs& a, const TileShar
     for (int i = lane; i < 256; i += 64) S.Abb[i] = 0.0;
     for (int i = lane; i < 96; i += 64) S.Gb[i] = 0.0;
     if (lane < 16) S.xdb[lane] = 0.0;
-    if (lane == 0) res_body_phase(xs, u_all + ((long)kp * S.B + S.b) * 6, a.dp, S.ctx, S.xdb, S.Abb, S.Gb);
+    if (lane == 0) res_body_phase(xs, u_all + ((long)kp * S.B + S.b) * 6, &prm, S.ctx, S.xdb, S.Abb, S.Gb);
     wave_lds_sync();
     if (lane >= 64 - 18) {   // A_v G_b (3 x 6), one entry per lane, on lanes that carry no feature
       const int e = lane - (64 - 18), j = e / 6, k = e - 6 * j;
@@ -64,7 +64,7 @@ __device__ __forceinline__ void tile_service(const StreamArgs& a, const TileShar
       }
       if (lane == 0) sm[tile_sm::fix_word(par)] = 0.0;
       for (int f = lane; f < len; f += 64)   // fix_depth (vi_ekf.cpp:311): state here, covariance through the mailbox
-        res_fix_depth(xs + xZ + 5 * f, a.dp, &S.fixadd[par * N + f], &S.fixset[par * N + f], &sm[tile_sm::fix_word(par)], &flag);
+        res_fix_depth(xs + xZ + 5 * f, &prm, &S.fixadd[par * N + f], &S.fixset[par * N + f], &sm[tile_sm::fix_word(par)], &flag);
       par ^= 1;
       __syncthreads();  // B3p
       double dt_next = 0.0;
@@ -102,7 +102,7 @@ __device__ __forceinline__ void tile_service(const StreamArgs& a, const TileShar
   double* qptr = isfeat ? (xs + xZ + 5 * fid) : (xs + xATT);
   double* linptr = isfeat ? (xs + xZ + 5 * fid + 4) : (xs + ((jb < 0) ? 0 : ((jb < 6) ? jb : ((jb < 14) ? jb + 3 : 0))));
   const double rho_reset = uniform_f64(1.0 / (2.0 * prm.min_depth));
-  const double lz0 = uniform_f64(a.lambda[16]), lz1 = uniform_f64(a.lambda[17]);
+  const double lz0 = uniform_f64(a.lam(uniform_filter(S.b))[16]), lz1 = uniform_f64(a.lam(uniform_filter(S.b))[17]);
   const double L00 = uniform_f64(partial ? (lz0 + lz0 - lz0 * lz0) : 1.0), L01 = uniform_f64(partial ? (lz0 + lz1 - lz0 * lz1) : 1.0),
                L11 = uniform_f64(partial ? (lz1 + lz1 - lz1 * lz1) : 1.0);
   // lambda of this lane's rows (1 without the partial update); P row of a tile-space row q: q - (q >> 4) + 1 past the body tile

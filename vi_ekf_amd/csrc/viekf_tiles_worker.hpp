@@ -66,7 +66,7 @@ __device__ __forceinline__ void tile_worker(const StreamArgs& a, const TileShare
   constexpr int TW = NW * 64, TPW = Map::max_count(), CNT = Map::count(W);
   const int N = S.N, n = S.n, ld = a.ld, nf = S.nf, len = S.len, NQ = S.NQ;
   const int lane = tid & 63, l15 = lane & 15, lg = lane >> 4;
-  const DevParams& prm = *a.dp;
+  const DevParams& prm = a.prm(uniform_filter(S.b));
   double* P = a.P + S.si * n * ld;
   double* Pbc = S.Pbc;   // [nf][16]  P[16+row][k]: the body columns, in LDS during load and propagate
   double* Pbb = S.Pbb;   // [16][16]  row-major P_bb
@@ -204,7 +204,7 @@ __device__ __forceinline__ void tile_worker(const StreamArgs& a, const TileShare
         for (int k6 = 0; k6 < 6; k6++) o2 = __builtin_amdgcn_mfma_f64_16x16x4f64(z_op(cj, k6, false), z_op(ci, k6, true), o2, 0, 0, 0);
         if (TI == TJ) {   // + Qx on the diagonal (every slot, active or not: vi_ekf.cpp:139-144,304)
           const int pr = tile_prow(TI, l15, nf);
-          const double qx = (pr >= 0) ? a.Qx[max(pr, 0)] : 0.0;
+          const double qx = (pr >= 0) ? a.qx(uniform_filter(S.b))[max(pr, 0)] : 0.0;
 #pragma unroll
           for (int r = 0; r < 4; r++)
             if (lg + 4 * r == l15) o2[r] += qx;
