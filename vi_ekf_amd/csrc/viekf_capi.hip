@@ -250,7 +250,7 @@ int viekf_batch_describe(const viekf_batch* b, char* out, int32_t cap) {
     snprintf(buf + len, sizeof buf - len, "; P %s between launches",
              keeps_packed(b) ? "packed" : "canonical");
   } else {
-    const int bg = blocked_group(b, nullptr);
+    const int bg = blocked_group(b);
     if (bg > 0)
       snprintf(buf, sizeof buf, "%s + %s<512,%d> (P in HBM/L2, one pass per group of %d measurements, fp64 MFMA "
                "passes, lower triangle only)", (b->tune_stream_mfma != 2 && 3 * b->N <= 512) ? "k_propagate_wide (K = 24 records in LDS)" : "k_propagate_stream",

@@ -13,6 +13,7 @@
 #include "viekf_kernels_body.hpp"
 #include "viekf_kernels_depth.hpp"
 #include "viekf_kernels_generic.hpp"
+#include "viekf_kernels_grouped.hpp"
 #include "viekf_kernels_hooks.hpp"
 #include "viekf_kernels_lifecycle.hpp"
 #include "viekf_kernels_pixvel.hpp"
@@ -74,7 +75,7 @@ int launch_propagate(viekf_batch* b, const double* d_u, const double* d_dt, cons
   if (int rc = require_P(b, stream_mfma_ok(b) ? PForm::Lower : PForm::Full)) return rc;
   StreamArgs a = make_args(b, call_mask);
   if (stream_mfma_ok(b)) {   // feature/feature part on the fp64 matrix cores: reads and writes the lower triangle only
-    const size_t wlds = sizeof(double) * (size_t)WideLds(b->N, b->nxs).total;
+    const size_t wlds = WideLds(b->N, b->nxs, sizeof(BodyCtx)).bytes();
     if (b->tune_stream_mfma != 2 && 3 * b->N <= 512 && wlds <= 158 * 1024) {   // the K = 24 record form, records in LDS
       static size_t have[64] = {};
       if (int rc = raise_dyn_lds({&k_propagate_wide<512>}, wlds, have[b->device & 63])) return rc;
@@ -91,37 +92,12 @@ int launch_propagate(viekf_batch* b, const double* d_u, const double* d_dt, cons
   return VIEKF_OK;
 }
 
-// Group size of the grouped update (k_update_feat_blocked): the largest of 32 / 24 / 16 whose panel fits the LDS (fewer passes
-// over P for the narrower filters); 0 = the grouped kernel does not apply (then one pass per measurement).
-// (measured: at N = 64 groups of 32 are SLOWER than 16 -- 1.96 vs 1.83 ms per step, the sequential panel phase grows with the
-//  group -- while N = 100 gains 4 % from 24: the wider groups only where the passes dominate)
-// the look-ahead form of the grouped update (k_update_feat_panelsvc): groups of 16 -- the 48 rows of a group's features fit the
-// serving wave -- where its double-buffered LDS layout fits next to the panel (N <= 154 at groups of 16)
-bool panel_svc(const viekf_batch* b) {
-  if (b->tune_panel_svc == 0 || !(b->tune_block_group == 0 || b->tune_block_group == 16) || b->n > 512) return false;
-  const PsvLds PL(b->N, b->n, b->nxs, 16);
-  return sizeof(double) * (size_t)PL.total + 1024 <= 160 * 1024;
+// The grouped update of this batch, if any (grouped_choice, viekf_stream_lds.hpp: THE rule, with the LDS budget)
+GroupedChoice grouped(const viekf_batch* b) {
+  return grouped_choice(b->N, b->n, b->nxs, b->tune_block_group, b->tune_panel_svc, b->tune_stream_mfma);
 }
-
-int blocked_group(const viekf_batch* b, size_t* lds_bytes) {
-  if (!stream_mfma_ok(b) || b->n > 512) return 0;
-  if (panel_svc(b)) {
-    if (lds_bytes) *lds_bytes = sizeof(double) * (size_t)PsvLds(b->N, b->n, b->nxs, 16).total;
-    return 16;
-  }
-  auto fits = [&](int cand, size_t* bytes) {
-    const BlkLds BL(b->N, b->n, b->nxs, cand);
-    *bytes = sizeof(double) * (size_t)BL.total;
-    return *bytes + 1024 <= 160 * 1024;   // (+ the kernel's small static LDS)
-  };
-  size_t bytes = 0;
-  if (b->tune_block_group && fits(b->tune_block_group, &bytes)) { if (lds_bytes) *lds_bytes = bytes; return b->tune_block_group; }
-  for (int cand : {32, 24, 16}) {
-    if (cand > 16 && b->n <= 256) continue;
-    if (fits(cand, &bytes)) { if (lds_bytes) *lds_bytes = bytes; return cand; }
-  }
-  return 0;
-}
+bool panel_svc(const viekf_batch* b) { return grouped(b).kernel == GroupedKernel::panelsvc; }
+int blocked_group(const viekf_batch* b) { return grouped(b).BG; }   // measurements per group; 0: one pass per measurement
 
 int launch_update(viekf_batch* b, const double* d_z, const int* d_slot, int M, const double* d_R, int r_mode,
                   int* d_res) {
@@ -129,17 +105,19 @@ int launch_update(viekf_batch* b, const double* d_z, const int* d_slot, int M, c
   StreamArgs a = make_args(b);
   long rsb = 0, rsm = 0;
   r_strides(r_mode, M, &rsb, &rsm);
-  // wide P, several measurements: the blocked kernel (one HBM pass over P per group of BG measurements, fp64 MFMA pass)
-  size_t blds = 0;
-  const int bg = blocked_group(b, &blds);
-  if (M >= 1 && bg > 0) {   // (a single measurement too: a group of one, no mirror pass before it)
+  // wide P: a grouped kernel (one HBM pass over P per group of BG measurements, fp64 MFMA pass)
+  const GroupedChoice gc = grouped(b);
+  if (M >= 1 && gc.kernel != GroupedKernel::none) {   // (a single measurement too: a group of one, no mirror pass before it)
     typedef void (*blk_kernel_t)(StreamArgs, const double*, const int*, int, const double*, long, long, int*);
-    const bool sv = panel_svc(b);
-    const blk_kernel_t kern = sv ? k_update_feat_panelsvc<512, 16>
-                                 : (bg == 32 ? k_update_feat_blocked<512, 32> : (bg == 24 ? k_update_feat_blocked<512, 24> : k_update_feat_blocked<512, 16>));
+    const bool sv = gc.kernel == GroupedKernel::panelsvc;
+    const int bg = gc.BG;
+    const size_t blds = gc.bytes;
+    const blk_kernel_t kern = sv ? k_update_feat_panelsvc<kGroupedThreads, 16>
+                                 : (bg == 32 ? k_update_feat_blocked<kGroupedThreads, 32>
+                                             : (bg == 24 ? k_update_feat_blocked<kGroupedThreads, 24> : k_update_feat_blocked<kGroupedThreads, 16>));
     static size_t have[64][6] = {};
     if (int rc = raise_dyn_lds({kern}, blds, have[b->device & 63][(bg == 32 ? 2 : (bg == 24 ? 1 : 0)) + (sv ? 3 : 0)])) return rc;
-    hipLaunchKernelGGL(kern, dim3(b->B), dim3(512), blds, b->stream, a, d_z, d_slot, M, d_R, rsb, rsm, d_res);
+    hipLaunchKernelGGL(kern, dim3(b->B), dim3(kGroupedThreads), blds, b->stream, a, d_z, d_slot, M, d_R, rsb, rsm, d_res);
     b->book.wrote_live(PForm::Lower);   // (reads and writes the lower triangle only)
   } else {
     if (int rc = require_P(b, PForm::Full)) return rc;   // (the one-measurement kernel reads whole columns)
