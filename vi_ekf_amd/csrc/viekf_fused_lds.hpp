@@ -139,6 +139,21 @@ VIEKF_HD inline int res_mcap(int N) { return N > 64 ? 80 : 64; }
 // instruction stream they had before (profiles/serial_loads/).
 constexpr bool res_batched_loads(int RB, int NW) { return NW != 7 && RB != 8; }
 
+// Which kernels publish a feature's column pair with ONE store body per wave (extract_cols, res_worker).  build_resmap's lane pass
+// leaves no worker thread with two blocks of a common feature (N = 50 on <7,3>: one thread with one such pair), so the lanes of a
+// wave's slots that hold the published feature are disjoint: each moves its six oriented values and its row base into one set of
+// temporaries, and three 16-byte stores behind the slot loop serve them all -- where every matching (slot, wave) group ran three
+// stores of its own, each taking the VGPR -> LDS store path for about 13 cycles whether one lane is enabled or sixty-four.  A lane's
+// second match stores from its slot as before, behind a branch a wave without such a lane skips.  The same values reach the same
+// addresses, so results are bit for bit those of the per-slot form.  The gate covers the single-propagate kernels of <7,3>, the
+// instance this was measured on; the multi-propagate kernels keep the per-slot statements and serve as the bit-for-bit reference.
+// VIEKF_MERGED_PUBLISH=0 at build time restores every kernel, and a kernel whose gate is off compiles to the instruction stream it
+// had before.
+#ifndef VIEKF_MERGED_PUBLISH
+#define VIEKF_MERGED_PUBLISH 1
+#endif
+constexpr bool res_merged_publish(int RB, int NW, bool MP) { return (VIEKF_MERGED_PUBLISH) != 0 && !MP && RB == 7 && NW == 3; }
+
 struct ResLds {  // resident family; staged: res_batched_loads of the instance.  The words of sm: res_sm above
   int xs, Kt, Wt, Praw, lam, sm, fixadd, fixset, Z, phiff, Abb, Gb, Phibb, Mbb, Gdb, Pbb, T16, xdb, ctx, Pbc, PhibbT, Pd, PsiP, Pi, Xi, AvG, Lbc, mslot, mseq, mz, mR, img_len, total;
   VIEKF_HD ResLds(int N, int n, int nxs, bool staged, std::size_t ctx_bytes) {

@@ -14,6 +14,9 @@ bool yaml_get_string(const YamlMap& m, const std::string& key, std::string& out,
 int set_last_error(int code, const std::string& msg);
 // block ownership map [RB][64 * NWV] of the fused-step kernel (viekf_resmap.cpp); false when the blocks do not fit
 bool build_resmap(int N, int RB, int NWV, std::vector<int>& map, int* used_slots = nullptr);
+// its last pass (lanes permuted inside the groups): the (thread, feature) repeats left on worker wave w, and the assignment solver
+int resmap_wave_repeats(const std::vector<int>& map, int RB, int NWV, int w);
+std::vector<int> resmap_assign(const std::vector<std::vector<long>>& cost);
 
 // Column stride of P for num_features features (viekf_batch_create explains the choice)
 inline int cov_ld(int num_features) {

@@ -136,6 +136,7 @@ template <int RB, int TW, bool MP, int T = TW + 64, bool ZU = false, bool BL = t
 __device__ __forceinline__ void res_worker(const StreamArgs& a, const ResShared& S, int tid) {
   constexpr bool SU = res_setup_under_load(RB, TW / 64, MP);
   constexpr int RR = res_rotating_reads(RB, TW / 64, MP, ZU);   // parts: 1 update-loop sweep, 2 contraction
+  constexpr bool MG = res_merged_publish(RB, TW / 64, MP);      // extract_cols: one store body per wave
   const int N = S.N, n = S.n, ld = a.ld, nf = S.nf, len = S.len;
   double* P = a.P + S.si * n * ld;
   // SYMMETRIC ownership: of each unordered pair of feature blocks {I,J} only one is kept (I >= J); which thread keeps it in
@@ -514,6 +515,42 @@ __device__ __forceinline__ void res_worker(const StreamArgs& a, const ResShared&
   // service wave, which turns them into the gain rows: the pair {I, slot} is held either as block (I, slot) (its columns
   // 0,1) or, transposed, as block (slot, J = I) (its rows 0,1).
   auto extract_cols = [&](int slot, double* Pw) {
+    if (MG) {   // merged (res_merged_publish): the lanes of this wave's slots that hold feature `slot` are disjoint but for the few
+                // repeats the map leaves -- one set of temporaries, ONE store body behind the slot loop
+      double a0 = 0.0, a1 = 0.0, b0 = 0.0, b1 = 0.0, c0 = 0.0, c1 = 0.0;
+      int base = 0;
+      bool matched = false;
+#pragma unroll
+      for (int ia = 0; ia < RB; ia++) {
+        const int I = Ib[ia], J = Jb[ia];
+        const bool asrow = J == slot;
+        const bool ascol = !asrow && I == slot;
+        if (vb[ia] && (asrow || ascol)) {
+          const int bs = 16 + 3 * (asrow ? I : J);
+          const double x0 = pb[ia][0], x1 = asrow ? pb[ia][1] : pb[ia][3];
+          const double y0 = asrow ? pb[ia][3] : pb[ia][1], y1 = pb[ia][4];
+          const double z0 = asrow ? pb[ia][6] : pb[ia][2], z1 = asrow ? pb[ia][7] : pb[ia][5];
+          // (this form is the measured one.  The second match in a pass of its own behind the merged body -- no register copies
+          //  around the `else`, 4 more spilled SGPRs -- timed 1.4 % slower than this form at the headline size, slower than the
+          //  per-slot statements too: profiles/merged_publish/README.md)
+          if (!matched) {
+            a0 = x0; a1 = x1; b0 = y0; b1 = y1; c0 = z0; c1 = z1;
+            base = bs;
+            matched = true;
+          } else {   // a thread's second block of this feature (a repeat the map could not remove): from its slot, as before
+            *reinterpret_cast<double2*>(Pw + 2 * (bs + 0)) = make_double2(x0, x1);
+            *reinterpret_cast<double2*>(Pw + 2 * (bs + 1)) = make_double2(y0, y1);
+            *reinterpret_cast<double2*>(Pw + 2 * (bs + 2)) = make_double2(z0, z1);
+          }
+        }
+      }
+      if (matched) {
+        *reinterpret_cast<double2*>(Pw + 2 * (base + 0)) = make_double2(a0, a1);
+        *reinterpret_cast<double2*>(Pw + 2 * (base + 1)) = make_double2(b0, b1);
+        *reinterpret_cast<double2*>(Pw + 2 * (base + 2)) = make_double2(c0, c1);
+      }
+      return;
+    }
 #pragma unroll
     for (int ia = 0; ia < RB; ia++) {
       const int I = Ib[ia], J = Jb[ia];

@@ -177,7 +177,106 @@ bool viekf::build_resmap(int N, int RB, int NWV, std::vector<int>& map, int* use
     used = std::max(used, dst);
   }
   if (used_slots) *used_slots = used;
+  // Which LANE of its group a block sits in is free too (slot 0 of the threads t < N keeps the diagonal blocks): lanes are
+  // permuted inside each (slot, wave) group until no worker thread holds two blocks with a common feature, or as few such
+  // (thread, feature) repeats as the search reaches.  The lanes of a wave's slots that hold feature s are then disjoint, and
+  // the wave publishes the column pair of s from all its slots with ONE store body (res_merged_publish).  Group by group, the
+  // blocks of a group are re-assigned to its lanes at the least number of repeats against the thread's other slots (an
+  // assignment problem of at most 64 x 64), and among those with the fewest blocks moved; rounds over a wave's groups repeat
+  // while the count falls.  A full 8 x 8 tile stays conflict-free in its operand reads under any permutation of its lanes (its
+  // 8 rows I and 8 columns J are consecutive features: 16-byte rows 3 apart, distinct modulo the 16 rows of the 64 banks).
+  for (int w = 0; w < NWV; w++)
+    for (int round = 0, before = resmap_wave_repeats(map, RB, NWV, w); before > 0 && round < 8; round++) {
+      for (int sl = 0; sl < used; sl++) {
+        std::vector<int> lanes;
+        for (int l = 0; l < 64; l++)
+          if (!(sl == 0 && 64 * w + l < N)) lanes.push_back(l);
+        const int m = (int)lanes.size();
+        if (m < 2) continue;
+        // cnt[q][f]: how many OTHER slots of lane lanes[q] hold feature f
+        std::vector<std::vector<unsigned char>> cnt(m, std::vector<unsigned char>(256, 0));
+        for (int q = 0; q < m; q++)
+          for (int s2 = 0; s2 < RB; s2++) {
+            const int e = map[(size_t)s2 * TW + 64 * w + lanes[q]];
+            if (s2 == sl || !(e >> 16)) continue;
+            cnt[q][e & 0xff]++;
+            if (((e >> 8) & 0xff) != (e & 0xff)) cnt[q][(e >> 8) & 0xff]++;
+          }
+        std::vector<int> ent(m);
+        for (int p = 0; p < m; p++) ent[p] = map[(size_t)sl * TW + 64 * w + lanes[p]];
+        std::vector<std::vector<long>> cost(m, std::vector<long>(m, 0));
+        for (int p = 0; p < m; p++)
+          for (int q = 0; q < m; q++) {
+            long c = 0;
+            if (ent[p] >> 16) c = (cnt[q][ent[p] & 0xff] ? 1 : 0) + (cnt[q][(ent[p] >> 8) & 0xff] ? 1 : 0);
+            cost[p][q] = c * 1024 + (p != q ? 1 : 0);
+          }
+        const std::vector<int> to = resmap_assign(cost);
+        for (int p = 0; p < m; p++) map[(size_t)sl * TW + 64 * w + lanes[to[p]]] = ent[p];
+      }
+      const int after = resmap_wave_repeats(map, RB, NWV, w);
+      if (after >= before) break;
+      before = after;
+    }
   return true;
+}
+
+// (thread, feature) repeats of worker wave w: over its threads and the features, the blocks of the thread that hold the
+// feature, less one
+int viekf::resmap_wave_repeats(const std::vector<int>& map, int RB, int NWV, int w) {
+  const int TW = 64 * NWV;
+  int rep = 0;
+  for (int l = 0; l < 64; l++) {
+    int cnt[256] = {0};
+    for (int sl = 0; sl < RB; sl++) {
+      const int e = map[(size_t)sl * TW + 64 * w + l];
+      if (!(e >> 16)) continue;
+      const int I = e & 0xff, J = (e >> 8) & 0xff;
+      if (cnt[I]++) rep++;
+      if (J != I && cnt[J]++) rep++;
+    }
+  }
+  return rep;
+}
+
+// Assignment problem: row p goes to column to[p], every column taken once, the sum of cost[p][to[p]] the least (the Hungarian
+// method with potentials, O(m^3); deterministic)
+std::vector<int> viekf::resmap_assign(const std::vector<std::vector<long>>& cost) {
+  const int m = (int)cost.size();
+  const long INF = 1L << 60;
+  std::vector<long> u(m + 1, 0), v(m + 1, 0);
+  std::vector<int> p(m + 1, 0), way(m + 1, 0);
+  for (int i = 1; i <= m; i++) {
+    p[0] = i;
+    int j0 = 0;
+    std::vector<long> minv(m + 1, INF);
+    std::vector<char> usedc(m + 1, 0);
+    do {
+      usedc[j0] = 1;
+      const int i0 = p[j0];
+      long delta = INF;
+      int j1 = 0;
+      for (int j = 1; j <= m; j++) {
+        if (usedc[j]) continue;
+        const long cur = cost[i0 - 1][j - 1] - u[i0] - v[j];
+        if (cur < minv[j]) { minv[j] = cur; way[j] = j0; }
+        if (minv[j] < delta) { delta = minv[j]; j1 = j; }
+      }
+      for (int j = 0; j <= m; j++) {
+        if (usedc[j]) { u[p[j]] += delta; v[j] -= delta; }
+        else minv[j] -= delta;
+      }
+      j0 = j1;
+    } while (p[j0] != 0);
+    do {
+      const int j1 = way[j0];
+      p[j0] = p[j1];
+      j0 = j1;
+    } while (j0);
+  }
+  std::vector<int> to(m, 0);
+  for (int j = 1; j <= m; j++) to[p[j] - 1] = j - 1;
+  return to;
 }
 
 extern "C" {
@@ -192,6 +291,17 @@ int viekf_debug_build_resmap(int n_feat, int rb, int nw, int32_t* out) {   // re
   if (n_feat * (n_feat + 1) / 2 > rb * nw * 64 || !viekf::build_resmap(n_feat, rb, nw, map, &used)) return -1;
   for (size_t i = 0; i < map.size(); i++) out[i] = map[i];
   return used;
+}
+
+// diagnostic hook (not part of include/viekf.h; host arithmetic only): the (thread, feature) repeats the map's lane pass left,
+// per worker wave -> out[nw]; returns their sum, -1 when the blocks do not fit.  tests/test_resmap_repeats_cpu.py recounts them.
+int viekf_debug_resmap_repeats(int n_feat, int rb, int nw, int32_t* out) {
+  std::vector<int> map;
+  if (n_feat < 1 || rb < 1 || nw < 1 || !out) return -1;
+  if (n_feat * (n_feat + 1) / 2 > rb * nw * 64 || !viekf::build_resmap(n_feat, rb, nw, map)) return -1;
+  int sum = 0;
+  for (int w = 0; w < nw; w++) sum += out[w] = viekf::resmap_wave_repeats(map, rb, nw, w);
+  return sum;
 }
 
 // diagnostic hook (not part of include/viekf.h): row i of the resident dispatch table (viekf_instance_rows.hpp, the index
